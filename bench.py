@@ -6,15 +6,30 @@ over one resident synthetic batch (hsi U[0,1) [64,144,9,9], lidar U[0,1) [64,1,9
 N: for N > 1 the gradient leaves the backward in three head-first buckets whose RCCL all-reduces run
 on a side stream while the backward continues (parallel.GradExchange), and AdamW waits for the last.
 
-  python bench.py [--gpus N --steps K --warmup W] [--precision fp32|bf16]   (torch.distributed.run for N > 1)
+  python bench.py [--gpus N --steps K --warmup W] [--precision fp32|bf16] [--dump-outputs DIR] [--full]
+  (torch.distributed.run for N > 1)
 
 `--precision` picks the headline step's GEMM operand precision (fp32 = the parity mode, default;
 bf16 = BASELINE config 2: bf16 operands, fp32 accumulation, fp32 master weights / scan state /
-norm statistics).  At N = 1 the line also carries the other precision's step (`config2_bf16`), the
-whole-image inference leg (`f1_test`), and the config-4/5 legs.
+norm statistics).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant
-kernel (HIP-event timed inside this process) and `cpu_baseline` (the CPU oracle, rank 0, N=1).
+A plain run does only what the headline figure needs: it builds the step (W eager warm-up steps, at
+least 3, then the capture), replays it untimed for WARM_S seconds, rewinds the training state to the
+one the capture left (so the K timed steps start from the same weights and optimizer moments in
+every run, however many untimed replays the clock allowed), times K steps and prints ONE JSON line on
+rank 0 (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration,
+`final_loss`, `model_flops_util`).
+
+`--dump-outputs DIR` then writes what the last timed step handed its caller, as float32 .npy files:
+`loss.npy` (the step's loss, [1]), `grad.npy` (the flat gradient, `model.flat_params.grad`) and
+`params.npy` (the flat parameter buffer after that step's AdamW update).  Inputs and initial weights
+are seeded, so two builds run with the same arguments can be compared file by file.
+
+`--full` adds every other measurement to the line: the step with a `loss.item()` sync and with
+on-device batch assembly, `roofline` / `roofline_gemm` for the dominant kernel and the largest GEMM
+(HIP-event timed inside this process), and at N = 1 the other precision's step (`config2_bf16`), the
+config-4/5 legs, the whole-image inference leg (`f1_test`), the `train()` loop leg and `cpu_baseline`
+(the CPU oracle, rank 0); the `--no-*` options leave single legs of a full run out.
 """
 import argparse
 import contextlib
@@ -44,6 +59,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss / flat gradient / updated flat "
+                         "parameters as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (loss.item() / batch-assembly variants, rooflines, other "
+                         "precision, config 4/5, whole-image test(), train() loop, CPU baselines)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-s2eft", action="store_true")
@@ -614,7 +635,7 @@ def build_step(dev, precision, world, rank, batch, exchange, warmup, use_graph):
     w[0] = 0.0
     crit = CrossEntropyLoss(weight=w.to(dev))
     hsi, lidar, target = synthetic(batch, 1000 + rank, dev)
-    holder = {}
+    holder = {"opt": opt}
 
     def body():
         holder["loss"] = fused_train_step(model, crit, hsi, lidar, target, optimizer=opt, exchange=exchange)
@@ -671,10 +692,34 @@ def warm(step, dev, seconds, world=1):
     return 5 + int(n.item())
 
 
-def time_steps(step, dev, steps, world, warm_s=WARM_S):
+def training_state(model, opt):
+    """Every tensor a training step updates in place: the flat parameter buffer, the BatchNorm
+    buffers, and the fused AdamW's moments and step counter."""
+    state = [model.flat_params.data] + [b.data for b in model.buffers()]
+    if opt._dev is not None:
+        state += [opt._dev[k] for k in ("m", "v", "step")]
+    return state
+
+
+def snapshot(model, opt):
+    """Returns rewind(): copies the training state as it is now back into place (same addresses, so
+    a captured step keeps replaying on it)."""
+    state = training_state(model, opt)
+    saved = [t.clone() for t in state]
+
+    def rewind():
+        for t, s in zip(state, saved):
+            t.copy_(s)
+    return rewind
+
+
+def time_steps(step, dev, steps, world, warm_s=WARM_S, rewind=None):
     """K steps bracketed by barrier + synchronize on both sides; max over ranks.  Preceded by
-    `warm_s` seconds of untimed replays."""
+    `warm_s` seconds of untimed replays, after which `rewind()` (snapshot) puts the training state
+    back, so the timed steps compute the same thing whatever number of replays the clock allowed."""
     warm(step, dev, warm_s, world)
+    if rewind is not None:
+        rewind()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -719,6 +764,15 @@ def bf16_gemm_roofline(model, batch, reps):
             "bound": "mfma", "achieved": round(achieved, 3), "peak": PEAK_BF16_MFMA_TFLOPS, "unit": "TFLOP/s",
             "frac": round(achieved / PEAK_BF16_MFMA_TFLOPS, 5), "avg_launch_us": round(t * 1e6, 2),
             "flop_per_launch": flops}
+
+
+def dump_outputs(path, model, holder):
+    """What the last timed step handed its caller, as float32 .npy files under `path`."""
+    os.makedirs(path, exist_ok=True)
+    flat = model.flat_params
+    arrays = {"loss": holder["loss"].detach().reshape(1), "grad": flat.grad.detach(), "params": flat.detach()}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
 
 
 def mfu(value_per_gpu, peak):
@@ -782,33 +836,9 @@ def f1_leg(dev, seed, cpu):
     return out, (cpu_leg if cpu else None)
 
 
-def main():
-    args = parse()
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if world > 1:
-        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    elif args.force_exchange:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29533")
-        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", local))
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-
-    exchange = world > 1 or args.force_exchange
-    log(f"rank {rank}/{world}: building the {args.precision} step")
-    step, model, (hsi, lidar, target), holder, launch = build_step(
-        dev, args.precision, world, rank, args.batch, exchange, args.warmup, not args.no_graph)
-    if args.roofline_only:
-        out = {"roofline": dominant_kernel_roofline(model, args.batch, args.kernel_reps),
-               "roofline_gemm": gemm_roofline(model, args.batch, args.kernel_reps)}
-        print(json.dumps(out), flush=True)
-        return
-    log(f"timing {args.steps} steps ({launch})")
-    elapsed = time_steps(step, dev, args.steps, world)
-    loss_val = float(holder["loss"].item())
-
+def full_legs(args, out, dev, world, rank, step, model, inputs, holder, elapsed):
+    """--full: every measurement beside the headline, added to the result line `out`."""
+    hsi, lidar, target = inputs
     # reference-loop variant: loss.item() host sync every step (model_utils.py:936)
     warm(step, dev, WARM_S / 2, world)
     t1 = time.perf_counter()
@@ -827,30 +857,14 @@ def main():
     roof = dominant_kernel_roofline(model, args.batch, args.kernel_reps)
     roof_gemm = (gemm_roofline if args.precision == "fp32" else bf16_gemm_roofline)(model, args.batch,
                                                                                      args.kernel_reps)
-    patches = world * args.batch * args.steps
-    value = patches / elapsed
-    peak = PEAK_FP32_MFMA_TFLOPS if args.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
-    out = {
-        "metric": "training patches/sec, 9×9 HSI(144)+LiDAR patch, batch 64, 1/2/4/8 GPU",
-        "value": round(value, 1), "unit": "patches/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision,
-        "data": "synthetic (U[0,1) HSI/LiDAR patches, random-init weights, resident in HBM)",
-        "config": {"workload": "ViT-CNN (Multimodality_Mamba) train step, Houston2013 shape 144+1 bands, 9x9, "
-                               "16 classes", "global_batch": world * args.batch, "per_gpu_batch": args.batch,
-                   "parallelism": f"dp{world}", "launch": launch,
-                   "gradient_exchange": (None if not exchange else
-                                         "RCCL all-reduce of 3 head-first buckets on a side stream, overlapped "
-                                         "with the backward; 1/world folded into AdamW")},
+    out.update({
         "ms_per_step_with_loss_item": round(ms_sync, 4),
         "value_with_loss_item": round(world * args.batch / ms_sync * 1e3, 1),
         "ms_per_step_with_batch_assembly": round(ms_asm, 4),
         "value_with_batch_assembly": round(world * args.batch / ms_asm * 1e3, 1),
-        "final_loss": round(loss_val, 6),
-        "model_flops_util": mfu(value / world, peak),
         "roofline": roof,
         "roofline_gemm": roof_gemm,
-    }
+    })
     cpu_legs = []
     if world == 1 and not args.no_s2eft:
         other = "bf16" if args.precision == "fp32" else "fp32"
@@ -881,6 +895,57 @@ def main():
         for c in cpu_legs:
             if c is not None:
                 c()
+
+
+def main():
+    args = parse()
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if world > 1:
+        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+    elif args.force_exchange:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29533")
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", local))
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+
+    exchange = world > 1 or args.force_exchange
+    log(f"rank {rank}/{world}: building the {args.precision} step")
+    step, model, (hsi, lidar, target), holder, launch = build_step(
+        dev, args.precision, world, rank, args.batch, exchange, args.warmup, not args.no_graph)
+    if args.roofline_only:
+        out = {"roofline": dominant_kernel_roofline(model, args.batch, args.kernel_reps),
+               "roofline_gemm": gemm_roofline(model, args.batch, args.kernel_reps)}
+        print(json.dumps(out), flush=True)
+        return
+    log(f"timing {args.steps} steps ({launch})")
+    elapsed = time_steps(step, dev, args.steps, world, rewind=snapshot(model, holder["opt"]))
+    loss_val = float(holder["loss"].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, holder)
+
+    patches = world * args.batch * args.steps
+    value = patches / elapsed
+    peak = PEAK_FP32_MFMA_TFLOPS if args.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
+    out = {
+        "metric": "training patches/sec, 9×9 HSI(144)+LiDAR patch, batch 64, 1/2/4/8 GPU",
+        "value": round(value, 1), "unit": "patches/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision,
+        "data": "synthetic (U[0,1) HSI/LiDAR patches, random-init weights, resident in HBM)",
+        "config": {"workload": "ViT-CNN (Multimodality_Mamba) train step, Houston2013 shape 144+1 bands, 9x9, "
+                               "16 classes", "global_batch": world * args.batch, "per_gpu_batch": args.batch,
+                   "parallelism": f"dp{world}", "launch": launch,
+                   "gradient_exchange": (None if not exchange else
+                                         "RCCL all-reduce of 3 head-first buckets on a side stream, overlapped "
+                                         "with the backward; 1/world folded into AdamW")},
+        "final_loss": round(loss_val, 6),
+        "model_flops_util": mfu(value / world, peak),
+    }
+    if args.full:
+        full_legs(args, out, dev, world, rank, step, model, (hsi, lidar, target), holder, elapsed)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

@@ -1,14 +1,10 @@
 """vitcnn_amd.launch: the reference CLI (main.py) patched for the MI355X path (VERDICT r2 missing item 2).
 
-The patch is checked on the reference's own main.py text when the reference tree is present (the
-build container; it is read as text and compiled, never executed -- it needs visdom and the .mat
-datasets), and on a synthetic main.py carrying the same anchor lines everywhere else.
+The patch is checked on a synthetic main.py carrying the reference's anchor lines in the reference's
+order (the reference's own main.py is program text of another project and is not part of this
+repository; `patch_main_source` raises on a main.py whose anchors have drifted).
 """
-import os
-
 import pytest
-
-REF_MAIN = "/root/reference/main.py"
 
 SYNTH = """import torch
 import sys
@@ -43,15 +39,11 @@ def _check(src):
 
 
 def test_patch_synthetic_main():
-    _check(SYNTH)
+    out = _check(SYNTH)
+    # the argparse namespace feeds get_model through hyperparams = vars(args) (main.py:311)
+    assert "hyperparams = vars(args)" in out
+    assert out.index("args = parser.parse_args()") < out.index("hyperparams = vars(args)")
     from vitcnn_amd.launch import patch_main_source
     with pytest.raises(RuntimeError, match="anchor"):
         patch_main_source(SYNTH.replace("args = parser.parse_args()", "args = parser.parse_known_args()[0]"))
 
-
-@pytest.mark.skipif(not os.path.exists(REF_MAIN), reason="reference tree absent (GPU box)")
-def test_patch_reference_main():
-    with open(REF_MAIN) as f:
-        out = _check(f.read())
-    # the argparse namespace feeds get_model through hyperparams = vars(args) (main.py:311)
-    assert "hyperparams = vars(args)" in out
