@@ -406,7 +406,9 @@ VC_API int vc_tl_fwd(int train, int B, int HW, int C, int S, const float* x, lon
                      const double* ws, double* stats, float* a, float* Z, hipStream_t stream);
 /* backward from dZ [B, S, C]: dx [B*HW, C] (ld lddx, overwritten) = (1/HW) a^T dZ + the pooled-path gradient
  * (argmax channel and mean), dparams (S x 5, overwritten); a = the attention maps vc_tl_fwd wrote (round 6: the
- * backward reads them instead of recomputing them; the round-5 `da` scratch argument is gone).  Two launches. */
+ * backward reads them instead of recomputing them; the round-5 `da` scratch argument is gone).  Two launches.
+ * Any C in 1..512 and any ldx / lddx >= C: the x and dZ rows are read by 16-B loads when C % 4 == 0, ldx % 4 == 0
+ * and both bases are 16-B aligned (bit-identical to the earlier kernels there), by guarded loads otherwise. */
 VC_API int vc_tl_bwd(int train, int B, int HW, int C, int S, const float* x, long ldx, const float* mx,
                      const float* avg, const int* amx, const float* params, const double* stats, const float* a,
                      const float* dZ, double* ws, float* dx, long lddx, float* dparams, hipStream_t stream);

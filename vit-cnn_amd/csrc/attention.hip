@@ -423,7 +423,8 @@ VC_API int vc_nonlocal_attn_fwd(int B, int S, int P, int Ci, const float* theta,
 #define VC_NL_FWD(PT_)                                                                                       \
   hipLaunchKernelGGL((nl_fwd<PT_, false>), dim3(B, vc_cdiv(S, NW)), dim3(NT), sm, stream, S, Ci, theta, pooled, \
                      att, o, 0, nullptr, 0L, nullptr, nullptr)
-  switch (P) {  // pooled key counts of 5x5 / 7x7 / 9x9 query grids, then generic buckets
+  switch (P) {  // pooled key counts of 5x5 / 7x7 / 9x9 query grids; 1: the 3x3 grid where the MFMA form is ruled out
+    case 1: VC_NL_FWD(1); break;
     case 4: VC_NL_FWD(4); break;
     case 9: VC_NL_FWD(9); break;
     case 16: VC_NL_FWD(16); break;
@@ -485,6 +486,7 @@ VC_API int vc_nonlocal_attn_bwd(int B, int S, int P, int Ci, const float* theta,
 #define VC_NL_BWD(PT_) \
   hipLaunchKernelGGL((nl_bwd<PT_>), dim3(B), dim3(NT), sm, stream, S, Ci, theta, pooled, att, dout, dtheta, dpooled)
   switch (P) {
+    case 1: VC_NL_BWD(1); break;   // (the 3x3 grid's one pooled key, Ci % 4 != 0)
     case 4: VC_NL_BWD(4); break;
     case 9: VC_NL_BWD(9); break;
     case 16: VC_NL_BWD(16); break;

@@ -505,7 +505,9 @@ VC_API int vc_rowchain_back_bwd(int rows, int Cout, int E, int D, const float* d
                                 const float* mean, const float* rstd, const float* ln_w, float* dt, float* ln_part,
                                 const float* w_out, const float* xz, const float* ypsum, float* dyp, float* dxz,
                                 hipStream_t stream) {
-  VC_REQUIRE(rows > 0 && Cout > 0 && Cout <= 256 && E > 0 && E <= 256 && D > 0);
+  // (dcd's rows are staged by 16-B loads, w_out's and the LN rows read as float4 fragments: whole groups of 4)
+  VC_REQUIRE(rows > 0 && Cout > 0 && Cout <= 256 && Cout % 4 == 0 && E > 0 && E <= 256 && E % 4 == 0 && D > 0);
+  VC_REQUIRE((((uintptr_t)dcd) & 15) == 0);
   VC_REQUIRE(dcd && w_cd && t2 && mean && rstd && ln_w && dt && ln_part && w_out && xz && ypsum && dyp && dxz);
   VC_REQUIRE_I32((long)rows * std::max(std::max(Cout, E), 2 * D));
   BwdChainArgs c{};
@@ -527,7 +529,8 @@ VC_API int vc_rowchain_front_bwd(int rows, int K0, int E, int Cin, const float* 
                                  const float* mean, const float* rstd, const float* ln_w, const float* res, float* dtt,
                                  float* ln_part, const float* w_embed, float* dx, float beta, const float* dx_add,
                                  hipStream_t stream) {
-  VC_REQUIRE(rows > 0 && K0 > 0 && K0 <= 256 && E > 0 && E <= 256 && Cin > 0);
+  VC_REQUIRE(rows > 0 && K0 > 0 && K0 <= 256 && K0 % 4 == 0 && E > 0 && E <= 256 && E % 4 == 0 && Cin > 0);
+  VC_REQUIRE((((uintptr_t)dxz) & 15) == 0);
   VC_REQUIRE(dxz && w_in && t && mean && rstd && ln_w && dtt && ln_part && (!dx || w_embed));
   VC_REQUIRE_I32((long)rows * std::max(std::max(K0, E), Cin));
   BwdChainArgs c{};

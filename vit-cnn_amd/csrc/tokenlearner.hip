@@ -221,6 +221,19 @@ __device__ __forceinline__ void mfma_k16(const f32x4& a, const f32x4& b, f32x4& 
 
 __device__ __forceinline__ f32x4 ld4_lds(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
+// elements k .. k + 3 of a row of n floats in global memory.  VEC: the row starts 16-B aligned and n % 4 == 0, so
+// the run is one whole 16-B load (the caller checks k < n).  Otherwise -- a row width or stride that is no multiple
+// of 4 -- four guarded loads: the last partial group is read up to n and no further, the rest of it is zero.
+template <bool VEC>
+__device__ __forceinline__ f32x4 ld4_row(const float* __restrict__ row, int k, int n) {
+  if (VEC) return *reinterpret_cast<const f32x4*>(row + k);
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (k + j < n) v[j] = row[k + j];
+  return v;
+}
+
 constexpr int TL_CT = 64;   // output columns (channels) per block of the pooling kernels
 
 // the token statistics of the block into LDS: tok_mean / tok_inv [S] (train: from the shared moments, which
@@ -358,7 +371,8 @@ __global__ __launch_bounds__(256) void tl_fwd_pool(int train, int B, int HW, int
 }
 
 // Backward part 1: grid (B, ceil(S / 16)); block 256.  da[b, s, q] = (1/HW) sum_c dZ[b, s, c] x[b, q, c] for
-// the block's 16 tokens (MFMA, both operands as float4 runs of their rows straight from L2), kept in registers;
+// the block's 16 tokens (MFMA, both operands as float4 runs of their rows straight from L2 -- ld4_row: one 16-B
+// load where the rows allow it (VEC), guarded loads for any other C / ldx), kept in registers;
 // then per token the fp64 sums over this sample's pixels of g1, g1 xh, g1 (m - mbar), g1 (v - vbar) ->
 // part[(b * S + s) * NBS + j] (summed over the pixel tiles in a fixed order), and (round 6) per pixel the fp64
 // sums over the block's 16 tokens of w0_s gi_s g1 and w1_s gi_s g1 (gi = gamma invstd) -> apart[((b * nsb +
@@ -370,6 +384,7 @@ __global__ __launch_bounds__(256) void tl_fwd_pool(int train, int B, int HW, int
 // selective-scan backward could not use; the per-token sums over the missing waves were exact zeros, so the
 // results are unchanged bit for bit
 constexpr int TLDA_W = 8;
+template <bool VEC>
 __global__ __launch_bounds__(64 * TLDA_W) void tl_bwd_da(int B, int HW, int C, int S, const float* __restrict__ x,
                                                          long ldx, const float* __restrict__ mx,
                                                          const float* __restrict__ avg, const float* __restrict__ par,
@@ -414,8 +429,8 @@ __global__ __launch_bounds__(64 * TLDA_W) void tl_bwd_da(int B, int HW, int C, i
         const int k = 16 * (kc0 + u) + 4 * g;
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         const bool kok = kc0 + u < nkc && k < C;
-        av[u] = (kok && sa < S) ? *reinterpret_cast<const f32x4*>(arow + k) : z;
-        bv[u] = (kok && qb < HW) ? *reinterpret_cast<const f32x4*>(brow + k) : z;
+        av[u] = (kok && sa < S) ? ld4_row<VEC>(arow, k, C) : z;
+        bv[u] = (kok && qb < HW) ? ld4_row<VEC>(brow, k, C) : z;
       }
 #pragma unroll
       for (int u = 0; u < KB; ++u)
@@ -493,7 +508,9 @@ __global__ __launch_bounds__(64 * TLDA_W) void tl_bwd_da(int B, int HW, int C, i
 // pixels at once for the model's patches); every sum is over tokens, so the results do not depend on QC.
 // LDS (dynamic): q4 [4][S][2], tsum [2][S], tst [2][S] doubles; dzl [S4][68], al [S4][QC + 4],
 // tpar [S][TPAR] (rounded up to 4), gq [2][QC] floats.
+// VEC: the dZ rows are 16-B aligned (C % 4 == 0), staged as float4 runs; otherwise element by element.
 constexpr int TLDX_RED = 8 * 4;   // doubles of tl_bwd_dx's static reduction buffer
+template <bool VEC>
 __global__ __launch_bounds__(256) void tl_bwd_dx(int train, int B, int HW, int C, int S, int QC,
                                                  const float* __restrict__ mx, const float* __restrict__ avg,
                                                  const int* __restrict__ amx, const float* __restrict__ par,
@@ -522,7 +539,7 @@ __global__ __launch_bounds__(256) void tl_bwd_dx(int train, int B, int HW, int C
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (s < S) {
       const float* src = dZ + ((long)b * S + s) * C + c;
-      if (c + 3 < C) v = *reinterpret_cast<const f32x4*>(src);
+      if (VEC && c + 3 < C) v = *reinterpret_cast<const f32x4*>(src);
       else
         for (int j = 0; j < 4; ++j)
           if (c + j < C) v[j] = src[j];
@@ -777,19 +794,29 @@ VC_API int vc_tl_fwd(int train, int B, int HW, int C, int S, const float* x, lon
 VC_API int vc_tl_bwd(int train, int B, int HW, int C, int S, const float* x, long ldx, const float* mx,
                      const float* avg, const int* amx, const float* params, const double* stats, const float* a,
                      const float* dZ, double* ws, float* dx, long lddx, float* dparams, hipStream_t stream) {
-  VC_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && ldx % 4 == 0 && S > 0 && ws && a && dx);
-  VC_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)dZ & 15) == 0);
+  VC_REQUIRE(B > 0 && HW > 0 && C > 0 && C <= 512 && ldx >= C && lddx >= C && S > 0 && ws && a && dx && x && dZ);
+  // 16-B row loads where every x and dZ row starts 16-B aligned; any other C / ldx / base takes guarded loads
+  const bool vec = C % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dZ & 15) == 0;
   const int QC = tl_bwd_qc(HW, S);
   VC_REQUIRE(QC > 0);
   VC_REQUIRE_I32((long)B * HW * (S > C ? S : C));
   double* part = ws + tl_pix_partials((long)B * HW);
   double* apart = part + (long)B * S * NBS;
   const int da_waves = std::min(TLDA_W, (HW + 15) / 16);
-  hipLaunchKernelGGL(tl_bwd_da, dim3(B, vc_cdiv(S, 16)), dim3(64 * da_waves), 0, stream, B, HW, C, S, x, ldx, mx, avg, params,
-                     stats, dZ, part, apart);
+  const dim3 da_grid(B, vc_cdiv(S, 16)), da_block(64 * da_waves), dx_grid(B, vc_cdiv(C, TL_CT));
+  if (vec)
+    hipLaunchKernelGGL(tl_bwd_da<true>, da_grid, da_block, 0, stream, B, HW, C, S, x, ldx, mx, avg, params, stats, dZ,
+                       part, apart);
+  else
+    hipLaunchKernelGGL(tl_bwd_da<false>, da_grid, da_block, 0, stream, B, HW, C, S, x, ldx, mx, avg, params, stats, dZ,
+                       part, apart);
   VC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(tl_bwd_dx, dim3(B, vc_cdiv(C, TL_CT)), dim3(256), tl_bwd_lds(S, QC), stream, train, B, HW, C, S,
-                     QC, mx, avg, amx, params, stats, a, dZ, part, apart, dx, lddx, dparams);
+  if (vec)
+    hipLaunchKernelGGL(tl_bwd_dx<true>, dx_grid, dim3(256), tl_bwd_lds(S, QC), stream, train, B, HW, C, S, QC, mx, avg,
+                       amx, params, stats, a, dZ, part, apart, dx, lddx, dparams);
+  else
+    hipLaunchKernelGGL(tl_bwd_dx<false>, dx_grid, dim3(256), tl_bwd_lds(S, QC), stream, train, B, HW, C, S, QC, mx,
+                       avg, amx, params, stats, a, dZ, part, apart, dx, lddx, dparams);
   VC_CHECK_LAUNCH();
   return VC_OK;
 }

@@ -165,6 +165,9 @@ def _check_supported(P, c1):
                          f"attention takes at most 16 pooled keys, ((P - 2) // 2)^2)")
     if c1 > 512:
         raise ValueError(f"ViT-CNN with {c1} HSI bands is not supported: at most 512")
+    if c1 < 2:
+        raise ValueError(f"ViT-CNN with {c1} HSI band(s) is not supported: the NonLocal attention of the second "
+                         f"block projects to in_channels1 // 2 inter-channels, which would be zero")
     L = lib()
     for hw, c, s in ((P * P, 256, (P - 2) ** 2), ((P - 2) ** 2, c1, (P - 4) ** 2)):
         if L.raw["vc_tl_check"](hw, c, s) != 0:
@@ -242,14 +245,18 @@ class Multimodality_Mamba(nn.Module):
         for n, p in active:
             covered[self._poff[n]:self._poff[n] + p.numel()] = True
         self._gaps = (~covered).nonzero().flatten().to(torch.int32).tolist()
-        for pfx in ("hsi1", "hsi2"):   # the stacked phi | g projection needs its four tensors adjacent
+        # the stacked phi | g projection needs its four tensors adjacent.  They are whenever Ci * Cout and Ci are
+        # multiples of PARAM_ALIGN (every band count divisible by 4) or the tensors are too small to be aligned;
+        # where the alignment of g's weight or bias opens a gap (e.g. 63 bands: Ci * Cout = 31 * 63), the block
+        # runs phi and g as two products over the same input instead (_pg_stacked[pfx] False)
+        self._pg_stacked: Dict[str, bool] = {}
+        for pfx in ("hsi1", "hsi2"):
             nl = pfx + ".FusionLayer.cross_attention."
             w, g_, b, gb = (self._poff.get(nl + k) for k in ("phi.0.weight", "g.0.weight", "phi.0.bias", "g.0.bias"))
             if w is not None:
                 ci = dict(named)[nl + "phi.0.bias"].numel()
                 cout = dict(named)[nl + "phi.0.weight"].numel() // ci
-                if not (g_ == w + ci * cout and b == g_ + ci * cout and gb == b + ci):
-                    raise RuntimeError(f"{nl}phi / g are not adjacent in the flat layout")
+                self._pg_stacked[pfx] = g_ == w + ci * cout and b == g_ + ci * cout and gb == b + ci
         device = named[0][1].device
         flat = torch.zeros(off, dtype=torch.float32, device=device)
         for n, p in named:
@@ -398,6 +405,29 @@ class Multimodality_Mamba(nn.Module):
         src = {}
         for kind, t in (("p", self._flat_store.detach()), ("b", self._bflat), ("i", self._iflat)):
             src[kind] = t.clone() if device is None else t.to(device, copy=True)
+        if self._n_params != self._n_elems:
+            # the copy of the parameters holds their elements only, packed in flat order: the alignment gaps of
+            # the flat layout are no part of a checkpoint (torch.save writes a view's whole storage)
+            comp = getattr(self, "_compact", None)
+            if comp is None:
+                # packed offsets, and the runs of the flat buffer between its gaps (a few dozen): (from, to, length)
+                coff, runs, o = {}, [], 0
+                for n in self._pnames:
+                    num, po = self._pmods[n][0]._parameters[self._pmods[n][1]].numel(), self._poff[n]
+                    coff[n] = o
+                    if runs and runs[-1][0] + runs[-1][2] == po:
+                        runs[-1][2] += num
+                    else:
+                        runs.append([po, o, num])
+                    o += num
+                comp = (coff, runs)
+                object.__setattr__(self, "_compact", comp)
+            coff, runs = comp
+            packed = torch.empty(self._n_elems, dtype=torch.float32, device=src["p"].device)
+            for po, o, num in runs:
+                packed[o:o + num].copy_(src["p"][po:po + num])
+            src["p"] = packed
+            rows = [(k, kind, coff[k] if kind == "p" else o, shape, n) for k, kind, o, shape, n in rows]
         out = OrderedDict((k, src[kind][o:o + n].view(shape)) for k, kind, o, shape, n in rows)
         if meta is not None:
             out._metadata = meta
@@ -927,12 +957,21 @@ class _Program:
             if _PG_LANE2 and self.lanes_on:
                 # the NonLocal phi | g projection of Fc on this lane, beside lane 1's local conv (_PG_LANE2)
                 nl = pfx + ".FusionLayer.cross_attention"
-                self.mm_nt(B * S, 2 * Ci, Cout, Fc, Cout, P[nl + ".phi.0.weight"], Cout, ws.f(pfx + ".PG", B * S * 2 * Ci),
-                           2 * Ci, bias=P[nl + ".phi.0.bias"])
+                self.pg_proj(pfx, B * S, Ci, Cout, Fc, ws.f(pfx + ".PG", B * S * 2 * Ci))
             e_fc = self.mark()
         with self.lane(1, e_fc):
             FM = self.glfusion(pfx, Fl, Fc, Cout, S, Ci, Pk, Hs)
             return FM, self.mark()
+
+    def pg_proj(self, pfx, M, Ci, Cout, Fc, PG):
+        """PG [M, 2 Ci] = the NonLocal phi | g projections of Fc: one product over their stacked weights / biases
+        where _build_flat keeps them adjacent, else one product each into the two column halves of PG"""
+        P, nl = self.P, pfx + ".FusionLayer.cross_attention"
+        if self.m._pg_stacked[pfx]:
+            self.mm_nt(M, 2 * Ci, Cout, Fc, Cout, P[nl + ".phi.0.weight"], Cout, PG, 2 * Ci, bias=P[nl + ".phi.0.bias"])
+            return
+        self.mm_nt(M, Ci, Cout, Fc, Cout, P[nl + ".phi.0.weight"], Cout, PG, 2 * Ci, bias=P[nl + ".phi.0.bias"])
+        self.mm_nt(M, Ci, Cout, Fc, Cout, P[nl + ".g.0.weight"], Cout, PG + F32 * Ci, 2 * Ci, bias=P[nl + ".g.0.bias"])
 
     def glfusion(self, pfx, Fl, Fc, Cout, S, Ci, Pk, Hs):
         """GLfusionBlock(x1 = channel, x2 = local): non-local cross attention (:140-159, :1107-1117)"""
@@ -944,9 +983,7 @@ class _Program:
         with self.gemm_group():
             self.mm_nt(M, Ci, Cout, Fl, Cout, P[nl + ".theta.weight"], Cout, TH, Ci, bias=P[nl + ".theta.bias"])
             if not (_PG_LANE2 and self.lanes_on):
-                # phi | g as one product over their stacked weights / biases (_build_flat keeps them adjacent)
-                self.mm_nt(M, 2 * Ci, Cout, Fc, Cout, P[nl + ".phi.0.weight"], Cout, PG, 2 * Ci,
-                           bias=P[nl + ".phi.0.bias"])
+                self.pg_proj(pfx, M, Ci, Cout, Fc, PG)
         PP = ws.f(pfx + ".PP", B * Pk * 2 * Ci)
         PA = ws.get(pfx + ".PA", B * Pk * 2 * Ci, torch.uint8).data_ptr()
         ATT, O = ws.f(pfx + ".ATT", M * Pk), ws.f(pfx + ".O", M * Ci)
@@ -1223,13 +1260,22 @@ class _Program:
             else:
                 self.L.vc_nonlocal_attn_bwd(B, S, Pk, Ci, TH, PP, ATT, dO, dTH, dPP, self.s)
                 self.L.vc_maxpool2_bwd(B, Hs, Hs, 2 * Ci, dPP, PA, dPG, 2 * Ci, self.s)
-            # phi | g (stacked, one weight + one data gradient) and theta: one grouped launch
+            # phi | g (stacked, one weight + one data gradient; or, where the flat layout could not keep them
+            # adjacent, phi then g from the two column halves of dPG) and theta: one grouped launch
             with self.gemm_group():
-                self.linear_bwd(nl + ".phi.0.weight", nl + ".phi.0.bias", dPG, M, 2 * Ci, Cout, Fc, Cout, dFc, 1.0,
-                                defer=True)
+                if self.m._pg_stacked[pfx]:
+                    self.linear_bwd(nl + ".phi.0.weight", nl + ".phi.0.bias", dPG, M, 2 * Ci, Cout, Fc, Cout, dFc, 1.0,
+                                    defer=True)
+                else:
+                    self.linear_bwd(nl + ".phi.0.weight", nl + ".phi.0.bias", dPG, M, Ci, Cout, Fc, Cout, dFc, 1.0,
+                                    lddy=2 * Ci, defer=True)
                 # dFl's last contribution; its epilogue applies the local conv's ReLU backward (mask Fl)
                 self.linear_bwd(nl + ".theta.weight", nl + ".theta.bias", dTH, M, Ci, Cout, Fl, Cout, dFl, 1.0,
                                 relu_mask=Fl, defer=True)
+            if not self.m._pg_stacked[pfx]:
+                # g's data gradient accumulates into dFc after phi's: a launch of its own, in program order
+                self.linear_bwd(nl + ".g.0.weight", nl + ".g.0.bias", dPG + F32 * Ci, M, Ci, Cout, Fc, Cout, dFc, 1.0,
+                                lddy=2 * Ci, defer=True)
             side = self.lanes_on and _CH_LANE != 1
             e_pg = self.mark() if side else None
             # local feature: BN -> conv3x3 -> ReLU backward (first accumulation into dX)
@@ -1266,7 +1312,7 @@ class _Program:
         Y, YP = f(pfx + ".Y", NDIR * rows * D), f(pfx + ".YP", rows * D)
         dU, dDTL = f(pfx + ".dU", NDIR * rows * D), f(pfx + ".dDTL", NDIR * rows * D)
         dXD, dXZ, dYP = f(pfx + ".dXD", NDIR * rows * XW), f(pfx + ".dXZ", rows * 2 * D), f(pfx + ".dYP", rows * D)
-        if self._chain_ok(blk):
+        if self._chain_back_bwd_ok(blk):
             # change_dim / ln1 / out_proj data gradients + the SiLU(z) gate backward in one launch; the
             # weight gradients and ln1's parameter reduction queued for the weight-gradient lane
             part = f(pfx + ".ln1part", self.L.vc_rowchain_ln_part_floats(rows, E))
@@ -1363,6 +1409,11 @@ class _Program:
         E = blk.embed
         return (self.row_chain and blk.cin <= 256 and blk.cin % 4 == 0 and E <= 256 and E % 4 == 0
                 and (E // 2) % 4 == 0 and blk.cout <= 256)
+
+    def _chain_back_bwd_ok(self, blk):
+        """vc_rowchain_back_bwd stages the change_dim gradient rows [rows, Cout] by 16-B loads: an output width
+        that is no multiple of 4 (hsi2 with such a band count) takes the separate launches in the backward"""
+        return self._chain_ok(blk) and blk.cout % 4 == 0
 
     def _ln_params(self, pfx, rows, E, part):
         """a LayerNorm's weight / bias gradients from a backward chain's partials: queued for the
