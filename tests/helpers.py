@@ -50,6 +50,50 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
+GUARD = 64        # elements of guard region after every kernel output of the per-kernel parity tests
+SENTINEL = -7.25  # exact in fp32; integer buffers use 0xA5 (uint8) / -7777
+
+
+class Guarded:
+    """A kernel output of `rows` rows of `ld` elements whose first `C` columns are the logical output,
+    followed by GUARD elements the kernel must not touch.  The logical part starts as NaN (or `init`, for
+    kernels that accumulate), the gap columns C .. ld - 1 and the guard as the sentinel; check() asserts
+    that gaps and guard are still bit-identical to it, so a store outside the logical output fails the
+    test instead of passing silently.  `lead` elements of sentinel precede the buffer (a base pointer that
+    is not 16-B aligned)."""
+
+    def __init__(self, rows, C, ld=None, init=None, dtype=torch.float32, device="cuda", lead=0):
+        ld = C if ld is None else ld
+        assert ld >= C
+        self.rows, self.C, self.ld, self.lead = rows, C, ld, lead
+        self.sent = SENTINEL if dtype.is_floating_point else {torch.uint8: 0xA5}.get(dtype, -7777)
+        self.flat = torch.full((lead + rows * ld + GUARD,), self.sent, dtype=dtype, device=device)
+        self.view = self.flat[lead:lead + rows * ld].view(rows, ld)
+        if init is not None:
+            self.view[:, :C] = init.reshape(rows, C).to(device=device, dtype=dtype)
+        elif dtype.is_floating_point:
+            self.view[:, :C] = float("nan")
+        self.ptr = self.flat.data_ptr() + lead * self.flat.element_size()
+
+    def check(self):
+        """synchronise; guards and gaps untouched; returns the logical output on the CPU"""
+        torch.cuda.synchronize()
+        flat = self.flat.cpu()
+        bits = {4: torch.int32, 8: torch.int64, 1: torch.uint8}[flat.element_size()]
+        want = torch.full((1,), self.sent, dtype=flat.dtype).view(bits)
+        body = flat[self.lead:self.lead + self.rows * self.ld].view(self.rows, self.ld)
+        assert bool((flat[:self.lead].view(bits) == want).all()), "store before the output"
+        assert bool((flat[self.lead + self.rows * self.ld:].view(bits) == want).all()), "store past the output (guard)"
+        assert bool((body[:, self.C:].contiguous().view(bits) == want).all()), "store into the gap columns"
+        return body[:, :self.C].clone()
+
+
+def within(kernel, shape, value, bound, inclusive=False):
+    """print the measured figure (pytest -s / -rP shows it: the DESIGN.md section 16 table), then assert it"""
+    print(f"PARITY {kernel} {shape} {value:.3e} {bound:.3e}")
+    assert (value <= bound) if inclusive else (value < bound), f"{kernel} {shape}: {value:.3e} vs bound {bound:.3e}"
+
+
 def relu_masks_from_workspace(model, B):
     """The HIP path's ReLU decisions for every conv3x3 / 1x1-fusion layer, as NCHW bool masks keyed by
     the oracle prefix (read from the saved channels-last post-ReLU activations `<pfx>.out`)."""
