@@ -60,19 +60,24 @@ class Guarded:
     kernels that accumulate), the gap columns C .. ld - 1 and the guard as the sentinel; check() asserts
     that gaps and guard are still bit-identical to it, so a store outside the logical output fails the
     test instead of passing silently.  `lead` elements of sentinel precede the buffer (a base pointer that
-    is not 16-B aligned)."""
+    is not 16-B aligned).  With `batch` > 1 the output is `batch` such matrices `stride` >= rows * ld elements
+    apart (a batched GEMM's C); the elements between two batches hold the sentinel too, `init` is
+    [batch, rows, C] and check() returns [batch, rows, C]."""
 
-    def __init__(self, rows, C, ld=None, init=None, dtype=torch.float32, device="cuda", lead=0):
+    def __init__(self, rows, C, ld=None, init=None, dtype=torch.float32, device="cuda", lead=0, batch=1, stride=None):
         ld = C if ld is None else ld
-        assert ld >= C
-        self.rows, self.C, self.ld, self.lead = rows, C, ld, lead
+        stride = rows * ld if stride is None else stride
+        assert ld >= C and stride >= rows * ld and batch >= 1
+        self.rows, self.C, self.ld, self.lead, self.batch, self.stride = rows, C, ld, lead, batch, stride
+        self.span = (batch - 1) * stride + rows * ld
         self.sent = SENTINEL if dtype.is_floating_point else {torch.uint8: 0xA5}.get(dtype, -7777)
-        self.flat = torch.full((lead + rows * ld + GUARD,), self.sent, dtype=dtype, device=device)
-        self.view = self.flat[lead:lead + rows * ld].view(rows, ld)
+        self.flat = torch.full((lead + self.span + GUARD,), self.sent, dtype=dtype, device=device)
+        mats = self.flat.as_strided((batch, rows, ld), (stride, ld, 1), lead)
+        self.view = mats[0] if batch == 1 else mats
         if init is not None:
-            self.view[:, :C] = init.reshape(rows, C).to(device=device, dtype=dtype)
+            mats[:, :, :C] = init.reshape(batch, rows, C).to(device=device, dtype=dtype)
         elif dtype.is_floating_point:
-            self.view[:, :C] = float("nan")
+            mats[:, :, :C] = float("nan")
         self.ptr = self.flat.data_ptr() + lead * self.flat.element_size()
 
     def check(self):
@@ -81,15 +86,40 @@ class Guarded:
         flat = self.flat.cpu()
         bits = {4: torch.int32, 8: torch.int64, 1: torch.uint8}[flat.element_size()]
         want = torch.full((1,), self.sent, dtype=flat.dtype).view(bits)
-        body = flat[self.lead:self.lead + self.rows * self.ld].view(self.rows, self.ld)
+        end = self.lead + self.span
+        mats = flat.as_strided((self.batch, self.rows, self.ld), (self.stride, self.ld, 1), self.lead)
         assert bool((flat[:self.lead].view(bits) == want).all()), "store before the output"
-        assert bool((flat[self.lead + self.rows * self.ld:].view(bits) == want).all()), "store past the output (guard)"
-        assert bool((body[:, self.C:].contiguous().view(bits) == want).all()), "store into the gap columns"
-        return body[:, :self.C].clone()
+        assert bool((flat[end:].view(bits) == want).all()), "store past the output (guard)"
+        assert bool((mats[:, :, self.C:].contiguous().view(bits) == want).all()), "store into the gap columns"
+        for b in range(self.batch - 1):   # rows * ld .. stride - 1 of every batch but the last
+            between = flat[self.lead + b * self.stride + self.rows * self.ld:self.lead + (b + 1) * self.stride]
+            assert bool((between.view(bits) == want).all()), "store between two batches"
+        out = mats[:, :, :self.C].clone()
+        return out[0] if self.batch == 1 else out
+
+
+class Poisoned:
+    """A kernel INPUT: the [rows, C] operand `t` (or [batch, rows, C], the batches `stride` elements apart)
+    in a buffer of leading dimension ld >= C, preceded by `lead` elements (1 to 3: a base pointer that is not
+    16-B aligned) and followed by GUARD elements.  Lead, gap columns C .. ld - 1, the elements between two
+    batches and the tail hold `poison` (NaN): a kernel that lets any element outside the logical operand
+    reach a stored output produces NaN there and fails its comparison.  (The accesses stay inside the
+    allocation, so a kernel that over-reads by less than GUARD elements is caught, not faulted.)"""
+
+    def __init__(self, t, ld=None, lead=0, stride=None, poison=float("nan"), device="cuda"):
+        t3 = t if t.dim() == 3 else t.unsqueeze(0)
+        batch, rows, C = t3.shape
+        ld = C if ld is None else ld
+        stride = rows * ld if stride is None else stride
+        assert ld >= C and stride >= rows * ld and 0 <= lead <= 3
+        self.rows, self.C, self.ld, self.lead, self.batch, self.stride = rows, C, ld, lead, batch, stride
+        self.flat = torch.full((lead + (batch - 1) * stride + rows * ld + GUARD,), poison, dtype=t.dtype, device=device)
+        self.flat.as_strided((batch, rows, ld), (stride, ld, 1), lead)[:, :, :C] = t3.to(device)
+        self.ptr = self.flat.data_ptr() + lead * self.flat.element_size()
 
 
 def within(kernel, shape, value, bound, inclusive=False):
-    """print the measured figure (pytest -s / -rP shows it: the DESIGN.md section 16 table), then assert it"""
+    """print the measured figure (pytest -s / -rP shows it: the DESIGN.md section 16 / 17 tables), then assert it"""
     print(f"PARITY {kernel} {shape} {value:.3e} {bound:.3e}")
     assert (value <= bound) if inclusive else (value < bound), f"{kernel} {shape}: {value:.3e} vs bound {bound:.3e}"
 

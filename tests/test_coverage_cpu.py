@@ -1,5 +1,6 @@
 """Guards that need no GPU: every entry point of include/vitcnn.h is named by some test, and the S2EFT /
-FusAtNet / glue entry points refuse invalid arguments on the host, before any launch."""
+FusAtNet / glue entry points, LayerNorm, vc_gemm and the Mamba scan refuse invalid arguments on the host, before
+any launch."""
 import glob
 import os
 import re
@@ -50,7 +51,19 @@ REJECTED = [
     ("adamw params not 16-B aligned", "vc_adamw", (8, 4, None, None, None, None, None, None)),
     ("adamw grads not 16-B aligned", "vc_adamw", (8, None, 4, None, None, None, None, None)),
     ("gate N = 4097", "vc_s2eft_gate_fwd", (1, 4097, 8, None, None, None, 0.4, None, None, None)),
+    ("layernorm C = 0", "vc_layernorm_fwd", (4, 0, None, 0, None, None, 1e-6, None, 0, None, None, None)),
+    ("layernorm C = 513", "vc_layernorm_fwd", (4, 513, None, 513, None, None, 1e-6, None, 513, None, None, None)),
+    ("gemm batch = 0", "vc_gemm", (0, 0, 4, 4, 4, 1.0, None, 4, 0, None, 4, 0, 0.0, None, 4, 0, 0, None, None, 0, 0, 0,
+                                   None, None, 0, None)),
+    ("gemm bias_grad with batch = 2", "vc_gemm", (1, 0, 4, 4, 4, 1.0, None, 4, 16, None, 4, 16, 0.0, None, 4, 16, 2, None,
+                                                  None, 0, 0, 0, 4, None, 0, None)),
+    ("scan D = 129", "vc_mamba_scan_fwd", (1, 4, 129, 9, 1, None, None, None, None, None, None, None, None, None, None)),
+    ("scan R = 65", "vc_mamba_scan_fwd", (1, 4, 72, 65, 1, None, None, None, None, None, None, None, None, None, None)),
 ]
+
+
+def test_scan_ckpt_floats_rejects_an_empty_batch():
+    assert _raw()["vc_mamba_scan_ckpt_floats"](0, 81, 72, 10) == -1
 
 
 @pytest.mark.parametrize("what,name,args", REJECTED, ids=[r[0] for r in REJECTED])

@@ -2,7 +2,9 @@
 
 This file covers the GEMMs, normalisation, convolution, Mamba, TokenLearner, NonLocal, cross-entropy and patch
 kernels; the S2EFT, FusAtNet, head, AdamW and glue kernels have test_s2eft_kernels_gpu.py,
-test_fusat_kernels_gpu.py and test_glue_kernels_gpu.py.  That every entry point of include/vitcnn.h is named by
+test_fusat_kernels_gpu.py and test_glue_kernels_gpu.py; the GEMMs and norms off their natural layouts (padded
+and misaligned operands, guarded outputs, tight workspaces) test_gemm_layouts_gpu.py and test_norm_layouts_gpu.py.
+That every entry point of include/vitcnn.h is named by
 some test is checked by test_coverage_cpu.py::test_every_entry_point_is_named_by_a_test.
 
 fp32 kernels, tolerance 1e-4 relative to the output's max |value| unless stated.

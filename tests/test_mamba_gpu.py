@@ -50,16 +50,18 @@ def _ref(xz, order, cw, cb, wx, wdt, bdt, alog, dsk, gate, B, L, D, R, ndir):
     return ys, leaves
 
 
-def _case(L, D, E):
+def _case(L, D, E, B=2, orders=None):
     """seeded float64 inputs of one mixer shape, the float64 reference output / gradients, and their
-    fp32 device copies"""
+    fp32 device copies; `orders`: the directions' token orders (default: the 10 scan orders of the
+    sqrt(L) x sqrt(L) grid)"""
     torch.manual_seed(0)
-    B, ndir, N = 2, 10, 16
+    N = 16
     R = math.ceil(E / 16)
     XW = R + 2 * N
     from vitcnn_amd.scan_orders import scan_orders, inverse
     n = int(round(L ** 0.5))
-    orders = scan_orders(n)
+    orders = scan_orders(n) if orders is None else orders
+    ndir = len(orders)
     order = torch.tensor(orders, dtype=torch.int64)
     f64 = torch.float64
     xz = torch.randn(B * L, 2 * D, dtype=f64)
@@ -72,7 +74,7 @@ def _case(L, D, E):
     ys_ref, leaves = _ref(xz, order, cw, cb, wx, wdt, bdt, alog, dsk, gate, B, L, D, R, ndir)
     (ys_ref.reshape(B * L, D) * dys).sum().backward()
     d = lambda t: t.to(torch.float32).contiguous().to(DEV)  # noqa: E731
-    c = dict(B=B, ndir=ndir, N=N, R=R, XW=XW, ref=ys_ref.detach().reshape(B * L, D), leaves=leaves,
+    c = dict(B=B, L=L, ndir=ndir, N=N, R=R, XW=XW, ref=ys_ref.detach().reshape(B * L, D), leaves=leaves,
              o32=torch.tensor(orders, dtype=torch.int32, device=DEV),
              inv32=torch.tensor([inverse(o) for o in orders], dtype=torch.int32, device=DEV))
     for nm, t in (("xz", xz), ("cw", cw), ("cb", cb), ("wx", wx), ("wdt", wdt), ("bdt", bdt), ("alog", alog),
@@ -264,3 +266,164 @@ def test_mamba_kernels_vs_float64(L, D, E, use_ckpt):
         r = leaf.grad.reshape(g_.shape)
         errs[nm] = float((g_.cpu().double() - r).abs().max() / r.abs().max())
     assert max(errs.values()) < 1e-4, errs
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Shapes off the models': even grids (L % 4 == 0: the last checkpoint segment is full), sequences shorter than /
+# equal to the conv's 4 taps and one segment (L = 1, 4), L % 4 in {2, 3} with 3 random permutations as directions,
+# B in {1, 3}, and D % 4 != 0, which only the unfused kernels take.  Every output is a helpers.Guarded buffer
+# (NaN, then a sentinel guard), xz and the upstream gradient helpers.Poisoned (NaN behind the operand).
+def _edge_orders(L, perm):
+    if not perm:
+        return None
+    g = torch.Generator().manual_seed(1234 + L)
+    return [torch.randperm(L, generator=g).tolist() for _ in range(3)]
+
+
+# L, D, E, B, random permutations
+EDGE_FUSED = [(16, 72, 144, 1, False), (36, 40, 80, 3, False), (1, 40, 80, 3, False), (4, 72, 144, 1, False),
+              (6, 40, 80, 1, True), (7, 72, 144, 3, True)]
+EDGE_UNFUSED = EDGE_FUSED + [(16, 18, 36, 1, False), (7, 18, 36, 3, True), (1, 18, 36, 1, False)]
+
+
+def _edge_run(lib, c, L, D, fused, use_ckpt=True):
+    """forward + backward of one mixer through the fused or the separate kernels, every output guarded; returns
+    (ysum, u, xdbl, the 9 gradients in _grad_errs' order)"""
+    from helpers import Guarded, Poisoned
+    B, ndir, N, R, XW = c["B"], c["ndir"], c["N"], c["R"], c["XW"]
+    s = torch.cuda.current_stream().cuda_stream
+    P = lambda t: t.data_ptr()  # noqa: E731
+    rows, nseq = ndir * B * L, ndir * B
+    xz, dys = Poisoned(c["xz"].cpu()), Poisoned(c["dys"].cpu())
+    ws = torch.empty(1 << 22, device=DEV)
+    U, XD, Y = Guarded(rows, D), Guarded(rows, XW), Guarded(rows, D)
+    CKP = Guarded(1, lib.vc_mamba_scan_ckpt_floats(B, L, D, ndir))
+    if fused:
+        assert lib.vc_mamba_scan_fwd_fused(B, L, D, R, ndir, xz.ptr, P(c["o32"]), P(c["cw"]), P(c["cb"]), P(c["wx"]),
+                                           P(c["wdt"]), P(c["bdt"]), P(c["alog"]), P(c["dsk"]), U.ptr, XD.ptr, Y.ptr,
+                                           CKP.ptr, s) == 0
+    else:
+        assert lib.vc_mamba_dirconv_fwd(B, L, D, ndir, P(c["o32"]), xz.ptr, P(c["cw"]), P(c["cb"]), U.ptr, s) == 0
+        assert lib.vc_gemm(0, 1, rows, XW, D, 1.0, U.ptr, D, 0, P(c["wx"]), D, 0, 0.0, XD.ptr, XW, 0, 1, None, None, 0,
+                           0, 0, None, P(ws), ws.numel(), s) == 0
+        assert lib.vc_mamba_scan_fwd(B, L, D, R, ndir, U.ptr, XD.ptr, P(c["o32"]), P(c["wdt"]), P(c["bdt"]),
+                                     P(c["alog"]), P(c["dsk"]), Y.ptr, CKP.ptr, s) == 0
+    YS, YP = Guarded(B * L, D), Guarded(B * L, D)
+    assert lib.vc_mamba_combine_fwd(B, L, D, ndir, P(c["inv32"]), P(c["gate"]), Y.ptr, xz.ptr, YP.ptr, YS.ptr, s) == 0
+    u_got, xd_got = U.check(), XD.check()
+    Y.check(), CKP.check(), YP.check()
+    ys_got = YS.check()
+
+    dU, dDTL, dXD = Guarded(rows, D), Guarded(rows, D), Guarded(rows, XW)
+    dXZ, dYP = Guarded(B * L, 2 * D), Guarded(B * L, D)
+    dA, dDs, dG = Guarded(D, N), Guarded(1, D), Guarded(1, ndir)
+    dCW, dCB = Guarded(D, 4), Guarded(1, D)
+    dWdt, dbdt, dWx = Guarded(D, R), Guarded(1, D), Guarded(XW, D)
+    assert lib.vc_mamba_gate_bwd(B, L, D, xz.ptr, YP.ptr, dys.ptr, dYP.ptr, dXZ.ptr, s) == 0
+    if fused:
+        CP = Guarded(1, nseq * 5 * D)
+        assert lib.vc_mamba_scan_bwd_fused(B, L, D, R, ndir, U.ptr, XD.ptr, P(c["o32"]), xz.ptr, P(c["cw"]), P(c["cb"]),
+                                           P(c["wx"]), P(c["wdt"]), P(c["bdt"]), P(c["alog"]), P(c["dsk"]), P(c["gate"]),
+                                           Y.ptr, dYP.ptr, CKP.ptr, dU.ptr, dDTL.ptr, dXD.ptr, CP.ptr, dA.ptr, dDs.ptr,
+                                           dG.ptr, P(ws), ws.numel(), s) == 0
+        assert lib.vc_mamba_dirconv_bwd_gather(B, L, D, ndir, P(c["inv32"]), P(c["cw"]), dU.ptr, dXZ.ptr, s) == 0
+        assert lib.vc_mamba_conv_params(B, D, ndir, CP.ptr, dCW.ptr, dCB.ptr, s) == 0
+        CP.check()
+    else:
+        assert lib.vc_mamba_scan_bwd(B, L, D, R, ndir, U.ptr, XD.ptr, P(c["o32"]), P(c["wdt"]), P(c["bdt"]),
+                                     P(c["alog"]), P(c["dsk"]), P(c["gate"]), Y.ptr, dYP.ptr,
+                                     CKP.ptr if use_ckpt else None, dU.ptr, dDTL.ptr, dXD.ptr, dA.ptr, dDs.ptr, dG.ptr,
+                                     P(ws), ws.numel(), s) == 0
+        assert lib.vc_gemm(0, 0, rows, R, D, 1.0, dDTL.ptr, D, 0, P(c["wdt"]), R, 0, 0.0, dXD.ptr, XW, 0, 1, None, None,
+                           0, 0, 0, None, P(ws), ws.numel(), s) == 0
+    assert lib.vc_gemm(1, 0, D, R, rows, 1.0, dDTL.ptr, D, 0, XD.ptr, XW, 0, 0.0, dWdt.ptr, R, 0, 1, None, None, 0, 0, 0,
+                       dbdt.ptr, P(ws), ws.numel(), s) == 0
+    assert lib.vc_gemm(1, 0, XW, D, rows, 1.0, dXD.ptr, XW, 0, U.ptr, D, 0, 0.0, dWx.ptr, D, 0, 1, None, None, 0, 0, 0,
+                       None, P(ws), ws.numel(), s) == 0
+    if not fused:
+        assert lib.vc_gemm(0, 0, rows, D, XW, 1.0, dXD.ptr, XW, 0, P(c["wx"]), D, 0, 1.0, dU.ptr, D, 0, 1, None, None, 0,
+                           0, 0, None, P(ws), ws.numel(), s) == 0
+        assert lib.vc_mamba_dirconv_bwd(B, L, D, ndir, P(c["o32"]), P(c["inv32"]), xz.ptr, P(c["cw"]), P(c["cb"]),
+                                        dU.ptr, dXZ.ptr, dCW.ptr, dCB.ptr, P(ws), ws.numel(), s) == 0
+    for t in (dU, dDTL, dXD, dYP):
+        t.check()
+    grads = [dXZ.check(), dCW.check(), dCB.check()[0], dWx.check(), dWdt.check(), dbdt.check()[0], dA.check(),
+             dDs.check()[0], dG.check()[0]]
+    return ys_got, u_got, xd_got, grads
+
+
+def _edge_assert(tag, shape, c, ys, grads):
+    from helpers import rel_err, within
+    err = float((ys.double() - c["ref"]).abs().max() / c["ref"].abs().max())
+    within(f"mamba {tag} forward", shape, err, 1e-5)
+    names = ["xz", "conv_w", "conv_b", "x_proj", "dt_w", "dt_b", "A_log", "D", "gate"]
+    for nm, g_, leaf in zip(names, grads, c["leaves"]):   # rel_err: a gradient that is exactly 0 (A_log at L = 1) is no 0 / 0
+        ref = leaf.grad.reshape(g_.shape)
+        if nm == "gate" and c["L"] == 1:
+            # L = 1: every direction is the same sequence, so ysum does not depend on the gate and the true gradient
+            # g_j (dg_j - sum_k g_k dg_k) is 0, the difference of equal terms dg_j = <dysum, ysum>: the fp32 result is
+            # held to 1e-4 of the terms' scale max_j g_j |dg|, not of the float64 rounding noise around 0
+            scale = float(torch.softmax(c["leaves"][8].detach(), 0).max() * (c["dys"].cpu().double() * c["ref"]).sum().abs())
+            within(f"mamba {tag} dgate (identical directions: of the terms' scale)", shape,
+                   float(g_.double().abs().max()) / scale, 1e-4)
+            assert float(ref.abs().max()) < 1e-12 * scale
+            continue
+        within(f"mamba {tag} d{nm}", shape, rel_err(g_.numpy(), ref.numpy()), 1e-4)
+
+
+@pytest.mark.parametrize("L,D,E,B,perm", EDGE_FUSED)
+def test_mamba_fused_edge_shapes(L, D, E, B, perm):
+    lib = _lib()
+    c = _case(L, D, E, B, _edge_orders(L, perm))
+    ys, u, xd, grads = _edge_run(lib, c, L, D, fused=True)
+    _edge_assert("fused", f"L={L},D={D},B={B},ndir={c['ndir']}", c, ys, grads)
+    # the fused front end's u is vc_mamba_dirconv_fwd's bit for bit, its xdbl the x_proj GEMM's to fp32 rounding
+    from helpers import Guarded
+    ndir, R, XW, rows = c["ndir"], c["R"], c["XW"], c["ndir"] * B * L
+    s = torch.cuda.current_stream().cuda_stream
+    U2, XD2, ws = Guarded(rows, D), Guarded(rows, XW), torch.empty(1 << 20, device=DEV)
+    P = lambda t: t.data_ptr()  # noqa: E731
+    assert lib.vc_mamba_dirconv_fwd(B, L, D, ndir, P(c["o32"]), P(c["xz"]), P(c["cw"]), P(c["cb"]), U2.ptr, s) == 0
+    assert lib.vc_gemm(0, 1, rows, XW, D, 1.0, U2.ptr, D, 0, P(c["wx"]), D, 0, 0.0, XD2.ptr, XW, 0, 1, None, None, 0, 0, 0,
+                       None, P(ws), ws.numel(), s) == 0
+    assert torch.equal(u, U2.check())
+    xd2 = XD2.check()
+    assert float((xd - xd2).abs().max() / xd2.abs().max()) < 1e-6
+
+
+@pytest.mark.parametrize("use_ckpt", [True, False])
+@pytest.mark.parametrize("L,D,E,B,perm", EDGE_UNFUSED)
+def test_mamba_kernels_edge_shapes(L, D, E, B, perm, use_ckpt):
+    lib = _lib()
+    c = _case(L, D, E, B, _edge_orders(L, perm))
+    ys, _, _, grads = _edge_run(lib, c, L, D, fused=False, use_ckpt=use_ckpt)
+    _edge_assert("kernels" + ("" if use_ckpt else " (states recomputed)"), f"L={L},D={D},B={B},ndir={c['ndir']}", c, ys,
+                 grads)
+
+
+@pytest.mark.parametrize("L,B", [(16, 1), (7, 3)])
+def test_mamba_fused_refuses_d_not_multiple_of_4(L, B):
+    """D = 18: vc_mamba_scan_fwd_fused / vc_mamba_scan_bwd_fused need float4 rows of W_x (D % 4 == 0) and must
+    return 1 before any launch (scan_fusable) although every pointer is valid; nothing is written"""
+    from helpers import Guarded
+    lib = _lib()
+    D, R, N, ndir = 18, 3, 16, 10
+    XW, rows = R + 2 * N, 10 * B * L
+    s = torch.cuda.current_stream().cuda_stream
+    z = lambda *shape: torch.zeros(*shape, device=DEV)  # noqa: E731
+    o32 = torch.zeros(ndir * L, dtype=torch.int32, device=DEV)
+    xz, cw, cb, wx, wdt, bdt, alog, dsk, gate = (z(B * L, 2 * D), z(D, 4), z(D), z(XW, D), z(D, R), z(D), z(D, N), z(D),
+                                                  z(ndir))
+    ws = torch.empty(1 << 20, device=DEV)
+    outs = [Guarded(rows, D), Guarded(rows, XW), Guarded(rows, D), Guarded(1, lib.vc_mamba_scan_ckpt_floats(B, L, D, ndir))]
+    P = lambda t: t.data_ptr()  # noqa: E731
+    assert lib.raw["vc_mamba_scan_fwd_fused"](B, L, D, R, ndir, P(xz), P(o32), P(cw), P(cb), P(wx), P(wdt), P(bdt),
+                                              P(alog), P(dsk), outs[0].ptr, outs[1].ptr, outs[2].ptr, outs[3].ptr, s) == 1
+    u, xd, y, dyp = z(rows, D), z(rows, XW), z(rows, D), z(B * L, D)
+    bouts = [Guarded(rows, D), Guarded(rows, D), Guarded(rows, XW), Guarded(1, ndir * B * 5 * D), Guarded(D, N),
+             Guarded(1, D), Guarded(1, ndir)]
+    assert lib.raw["vc_mamba_scan_bwd_fused"](B, L, D, R, ndir, P(u), P(xd), P(o32), P(xz), P(cw), P(cb), P(wx), P(wdt),
+                                              P(bdt), P(alog), P(dsk), P(gate), P(y), P(dyp), outs[3].ptr,
+                                              *[o.ptr for o in bouts], P(ws), ws.numel(), s) == 1
+    for o in outs + bouts:
+        assert torch.isnan(o.check()).all()
