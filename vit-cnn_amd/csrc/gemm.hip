@@ -10,6 +10,8 @@
 // every weight / input gradient of those.  Activations are channels-last [rows, C], so a
 // 1x1 conv is C[M,N] = X[M,K] * W[N,K]^T (transB=1) and its weight gradient is
 // dW[N,K] = dY[M,N]^T * X[M,K] (transA=1, split over M).
+#include <type_traits>
+
 #include "common.h"
 #include "mfma_tiles.h"
 
@@ -121,7 +123,7 @@ __device__ __forceinline__ float slab_sum(const float* p, long slab, int nsplit,
 // One 64x64 output tile (bx, by) of K slice / batch bz; tn x tm tiles per slice (the arrival-counter
 // index of the in-launch combine).  Shared by the single-problem kernel and the grouped one, which
 // own the LDS (As, Bs: BK * LDS_STRIDE floats each, `last`: one int).
-template <bool TA, bool TB, bool VA, bool VB, int PD>
+template <bool TA, bool TB, bool VA, bool VB>
 __device__ __forceinline__ void gemm_f32_tile(const GemmArgs& g, int bx, int by, int bz, int tn, int tm,
                                               float* __restrict__ As, float* __restrict__ Bs, int* last) {
   const int tid = threadIdx.x;
@@ -135,11 +137,10 @@ __device__ __forceinline__ void gemm_f32_tile(const GemmArgs& g, int bx, int by,
   const float* Bp = g.B + (long)zb * g.sB;
   const bool ones = g.Ne > g.N;
 
-  // PD register sets of staged operand tiles: the global loads of k-tiles t+1 .. t+PD-1 are in
-  // flight while tile t is multiplied (the small-grid GEMMs of the step are bound by the load
-  // latency of their few k-tiles, not by the MFMAs); the k order and the MFMA sequence are those of
-  // PD = 1, so the results are bit-identical for every depth.
-  float ra[PD][NE], rb[PD][NE];
+  // One register set of staged operand tiles: the global loads of k-tile t+1 are in flight while tile t is
+  // multiplied.  Deeper sets (bit-identical results) measured slower on the whole step -- the extra VGPRs cost
+  // more occupancy than the earlier loads save latency (profiles/r03_ab_gemm_pd.log) -- and were removed.
+  float ra[NE], rb[NE];
   auto a_at = [&](int gm, int gk) -> float {
     return (gm < g.M && gk < kend) ? (TA ? A[(long)gk * g.lda + gm] : A[(long)gm * g.lda + gk]) : 0.f;
   };
@@ -216,32 +217,24 @@ __device__ __forceinline__ void gemm_f32_tile(const GemmArgs& g, int bx, int by,
 
   const int fr = lane & 15, fk = lane >> 4;
   const int nk = kbeg < kend ? (kend - kbeg + BK - 1) / BK : 0;
+  if (nk > 0) load(kbeg, ra, rb);
+  for (int t = 0; t < nk; ++t) {
+    store(ra, rb);
+    __syncthreads();
+    if (t + 1 < nk) load(kbeg + (t + 1) * BK, ra, rb);
 #pragma unroll
-  for (int p = 0; p < PD; ++p)
-    if (p < nk) load(kbeg + p * BK, ra[p], rb[p]);
-  for (int t0 = 0; t0 < nk; t0 += PD) {
-#pragma unroll
-    for (int s = 0; s < PD; ++s) {
-      const int t = t0 + s;
-      if (t < nk) {
-        store(ra[s], rb[s]);
-        __syncthreads();
-        if (t + PD < nk) load(kbeg + (t + PD) * BK, ra[s], rb[s]);
-#pragma unroll
-        for (int ks = 0; ks < BK / 4; ++ks) {
-          const int kk = ks * 4 + fk;
-          const float a0 = As[kk * LDS_STRIDE + wm * 32 + fr];
-          const float a1 = As[kk * LDS_STRIDE + wm * 32 + 16 + fr];
-          const float b0 = Bs[kk * LDS_STRIDE + wn * 32 + fr];
-          const float b1 = Bs[kk * LDS_STRIDE + wn * 32 + 16 + fr];
-          acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-          acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-          acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-          acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        __syncthreads();
-      }
+    for (int ks = 0; ks < BK / 4; ++ks) {
+      const int kk = ks * 4 + fk;
+      const float a0 = As[kk * LDS_STRIDE + wm * 32 + fr];
+      const float a1 = As[kk * LDS_STRIDE + wm * 32 + 16 + fr];
+      const float b0 = Bs[kk * LDS_STRIDE + wn * 32 + fr];
+      const float b1 = Bs[kk * LDS_STRIDE + wn * 32 + 16 + fr];
+      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
     }
+    __syncthreads();
   }
 
   // C/D map of 16x16x4: col = lane & 15, row = (lane >> 4) * 4 + r
@@ -291,18 +284,19 @@ __device__ __forceinline__ void gemm_f32_tile(const GemmArgs& g, int bx, int by,
   if (tid == 0) __hip_atomic_store(&g.cnt[tile], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool TA, bool TB, bool VA, bool VB, int PD>
+template <bool TA, bool TB, bool VA, bool VB>
 __global__ __launch_bounds__(256) void gemm_f32_mfma(GemmArgs g) {
   __shared__ float As[BK * LDS_STRIDE];
   __shared__ float Bs[BK * LDS_STRIDE];
   __shared__ int last;
-  gemm_f32_tile<TA, TB, VA, VB, PD>(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, As, Bs, &last);
+  gemm_f32_tile<TA, TB, VA, VB>(g, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, As, Bs, &last);
 }
 
 // Grouped launch: up to GROUP_MAX independent problems in one grid (a horizontal fusion of GEMMs that
 // would otherwise be separate launches on one stream).  Block b belongs to the problem p with
 // start[p] <= b < start[p + 1] and runs its tile (b - start[p]) in (x fastest, y, z) order; the
-// (TA, TB, VA, VB) variant is a runtime switch (registers: the largest variant's).
+// (TA, TB, VA, VB) variant is a runtime switch (registers: the largest variant's).  The pipelined kernel's
+// grouped launch (gp::gemm_pipe_group) takes the same struct, with its own variant numbering.
 constexpr int GROUP_MAX = 8;
 struct GemmGroup {
   int n;
@@ -311,47 +305,41 @@ struct GemmGroup {
   GemmArgs g[GROUP_MAX];
 };
 
-// The kernel arguments are indexed with constants only (an unrolled select), so the problem's
-// descriptor is read with scalar loads from the argument segment instead of a dynamically indexed
-// private copy.
-struct GroupSel {
-  GemmArgs g;
-  int start, tn, tm, variant;
-};
-
-__device__ __forceinline__ GroupSel group_select(const GemmGroup& G, int b) {
-  GroupSel s;
-  s.g = G.g[0];
-  s.start = G.start[0];
-  s.tn = G.tn[0];
-  s.tm = G.tm[0];
-  s.variant = G.variant[0];
+// The problem that owns block b of a grouped grid of up to CAP problems, and element p of one of the
+// group's arrays.  The kernel arguments are indexed with constants only (unrolled selects), so the
+// problem's descriptor is read with scalar loads from the argument segment instead of a dynamically
+// indexed private copy.
+template <int CAP>
+__device__ __forceinline__ int group_owner(int n, const int (&start)[CAP + 1], int b) {
+  int p = 0;
 #pragma unroll
-  for (int k = 1; k < GROUP_MAX; ++k)
-    if (k < G.n && b >= G.start[k]) {
-      s.g = G.g[k];
-      s.start = G.start[k];
-      s.tn = G.tn[k];
-      s.tm = G.tm[k];
-      s.variant = G.variant[k];
-    }
-  return s;
+  for (int k = 1; k < CAP; ++k)
+    if (k < n && b >= start[k]) p = k;
+  return p;
 }
 
-template <int PD>
+template <class T, int CAP>
+__device__ __forceinline__ T group_pick(const T (&x)[CAP], int p) {
+  T v = x[0];
+#pragma unroll
+  for (int k = 1; k < CAP; ++k)
+    if (k == p) v = x[k];
+  return v;
+}
+
 __global__ __launch_bounds__(256) void gemm_f32_group(GemmGroup G) {
   __shared__ float As[BK * LDS_STRIDE];
   __shared__ float Bs[BK * LDS_STRIDE];
   __shared__ int last;
   const int b = blockIdx.x;
-  const GroupSel s = group_select(G, b);
-  const int local = b - s.start;
-  const int tn = s.tn, tm = s.tm;
+  const int p = group_owner<GROUP_MAX>(G.n, G.start, b);
+  const GemmArgs g = group_pick(G.g, p);
+  const int local = b - group_pick(G.start, p);
+  const int tn = group_pick(G.tn, p), tm = group_pick(G.tm, p);
   const int bx = local % tn, by = (local / tn) % tm, bz = local / (tn * tm);
-  const GemmArgs& g = s.g;
 #define VC_TILE(V_, TA_, TB_, VA_, VB_) \
-  case V_: gemm_f32_tile<TA_, TB_, VA_, VB_, PD>(g, bx, by, bz, tn, tm, As, Bs, &last); break;
-  switch (s.variant) {
+  case V_: gemm_f32_tile<TA_, TB_, VA_, VB_>(g, bx, by, bz, tn, tm, As, Bs, &last); break;
+  switch (group_pick(G.variant, p)) {
     VC_TILE(0, false, false, false, false) VC_TILE(1, false, false, false, true)
     VC_TILE(2, false, false, true, false) VC_TILE(3, false, false, true, true)
     VC_TILE(4, false, true, false, false) VC_TILE(5, false, true, false, true)
@@ -701,33 +689,25 @@ __device__ __forceinline__ void mma_ktile_bf(const char* As, const char* Bs, int
 // counter's index of the in-launch combine, g.cnt; null = slabs for a separate reduce).  `smem` is the
 // block's LDS ring (ring_bytes), shared by the single-problem and the grouped kernel.
 //
-// KS = 2 (fp32): twice the waves, the k-split pair of each wave tile sharing the ring -- wave half kh runs
-// sub-step kh of every k-tile (g2::mma_substep), so each SIMD holds two waves whose LDS waits and DMA
-// issue overlap the other's MFMAs (one wave per SIMD left the 16x16x4 issue idle ~half the time on a
-// one-block-per-CU grid); the halves' accumulators are g2's NC = 2 partials, summed acc0 + acc1 through
-// the idle ring before the epilogue, which the kh = 0 waves run.
+// (A k-split variant -- twice the waves, each half one 16-k sub-step of every k-tile -- was superseded by the
+// 8-wave 2 x 4 layout, profiles/r05_gemm_ks.log, and removed.)
 //
 // KM = 2 (round 6): each ring stage holds two consecutive 32-wide k-tiles (two A and two B images), so the block
 // runs one DMA wait + barrier per 64 of K instead of per 32 -- the per-k-tile overhead, not the MFMAs, sets the
 // time of the step's latency-bound shapes (more so with bf16 MFMAs, 1/8 of the fp32 count).  Same MFMAs in the
 // same order: bit-identical to KM = 1.
-template <int BM, int BN, int WM, int WN, bool TA, bool TB, int NS, bool BF = false, int KS = 1, int KM = 1>
+template <int BM, int BN, int WM, int WN, bool TA, bool TB, int NS, bool BF = false, int KM = 1>
 __device__ __forceinline__ void pipe_tile(const GemmArgs& g, int zb, int zs, int xn, int ym, int tn, int tm, int G,
                                           char* smem) {
-  constexpr int NWT = WM * WN;                  // waves per k-split half
-  constexpr int NW = NWT * KS, NTH = 64 * NW;   // all waves (they share the DMA of a stage)
+  constexpr int NW = WM * WN, NTH = 64 * NW;    // the waves (they share the DMA of a stage)
   constexpr int WTM = BM / WM, WTN = BN / WN;   // wave tile
   constexpr int MT = WTM / 16, NT = WTN / 16;
   constexpr int SA_B = BM * 128, SUB = (BM + BN) * 128, STAGE = KM * SUB;
   constexpr int LOADS = KM * (BM / 8 + BN / 8) / NW;   // DMA wave-instructions per wave and stage
   static_assert(NS >= 2 && NS <= 4, "ring depth");
-  static_assert(KM == 1 || (KM == 2 && KS == 1), "two k-tiles per stage: without k-split waves");
-  static_assert(KS == 1 || (KS == 2 && !BF), "k-split waves: fp32 only");
-  static_assert(KS == 1 || NWT * MT * NT * 4 * 64 * 4 <= ring_bytes<BM, BN, NS>(), "partials fit the ring");
+  static_assert(KM == 1 || KM == 2, "k-tiles per stage");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kh = wave / NWT, wt = wave % NWT;
-  const int wm = wt / WN, wn = wt % WN;
-  const bool out_wave = kh == 0;
+  const int wm = wave / WN, wn = wave % WN;
   const int z = zb * g.nsplit + zs;
   const int m0 = ym * BM, n0 = xn * BN;
   const int kbeg = zs * g.k_chunk;
@@ -789,29 +769,8 @@ __device__ __forceinline__ void pipe_tile(const GemmArgs& g, int zb, int zs, int
       if (KM > 1 && kbeg + (t * KM + u) * KT >= kend) break;   // a ragged last stage (uniform)
       const char* cur = smem + (t % NS) * STAGE + u * SUB;
       if constexpr (BF) mma_ktile_bf<MT, NT, SA, SB>(cur, cur + SA_B, wm * WTM, wn * WTN, lane, acc[0]);
-      else if constexpr (KS == 2) g2::mma_substep<MT, NT, SA, SB>(cur, cur + SA_B, wm * WTM, wn * WTN, lane, kh, acc[0]);
       else g2::mma_ktile<false, MT, NT, SA, SB, 1>(cur, cur + SA_B, wm * WTM, wn * WTN, lane, acc);
     }
-  }
-  if constexpr (KS == 2) {   // acc = sub-step-0 partial + sub-step-1 partial (g2's NC = 2 order)
-    float* xch = reinterpret_cast<float*>(smem);   // [NWT][MT][NT][4][64]
-    __syncthreads();                               // every wave past its last ring read
-    if (kh == 1)
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) xch[(((wt * MT + mi) * NT + ni) * 4 + r) * 64 + lane] = acc[0][mi][ni][r];
-    __syncthreads();
-    if (kh == 0)
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            acc[0][mi][ni][r] = acc[0][mi][ni][r] + xch[(((wt * MT + mi) * NT + ni) * 4 + r) * 64 + lane];
   }
 
   // C/D map of the 16x16 MFMAs: col = lane & 15, row = (lane >> 4) * 4 + r
@@ -827,7 +786,7 @@ __device__ __forceinline__ void pipe_tile(const GemmArgs& g, int zb, int zs, int
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int m = m0 + wm * WTM + mi * 16 + (lane >> 4) * 4 + r;
-          if (out_wave && m < g.M && n < g.N) {
+          if (m < g.M && n < g.N) {
             float* cp = g.C + (long)m * g.ldc + n;
             const float v = epilogue(g.epi, acc[0][mi][ni][r], cp, m, n);
             *cp = v;
@@ -847,7 +806,7 @@ __device__ __forceinline__ void pipe_tile(const GemmArgs& g, int zb, int zs, int
     // the WM row waves of the tile: through the idle LDS ring (all waves are past their last k-tile reads)
     double* red = reinterpret_cast<double*>(smem);   // [2][WM][BN]
     __syncthreads();
-    if (out_wave && lane < 16)
+    if (lane < 16)
 #pragma unroll
       for (int ni = 0; ni < NT; ++ni)
 #pragma unroll
@@ -871,7 +830,7 @@ __device__ __forceinline__ void pipe_tile(const GemmArgs& g, int zb, int zs, int
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wm * WTM + mi * 16 + (lane >> 4) * 4 + r;
         const int n = n0 + wn * WTN + ni * 16 + (lane & 15);
-        if (out_wave && m < g.M && n < g.Ne) {
+        if (m < g.M && n < g.Ne) {
           if (g.nsplit > 1) g.part[((long)z * g.M + m) * g.Ne + n] = acc[0][mi][ni][r];
           else store_out(g, zb, m, n, acc[0][mi][ni][r]);
         }
@@ -905,63 +864,37 @@ __device__ __forceinline__ void pipe_tile(const GemmArgs& g, int zb, int zs, int
   if (tid == 0) __hip_atomic_store(&g.cnt[tile], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int BM, int BN, int WM, int WN, bool TA, bool TB, int NS, bool BF = false, int KS = 1, int KM = 1>
-__global__ __launch_bounds__(64 * WM * WN * KS) void gemm_pipe(GemmArgs g, int tn, int tm, unsigned total, int G,
-                                                                int zfast) {
+template <int BM, int BN, int WM, int WN, bool TA, bool TB, int NS, bool BF = false, int KM = 1>
+__global__ __launch_bounds__(64 * WM * WN) void gemm_pipe(GemmArgs g, int tn, int tm, unsigned total, int G,
+                                                           int zfast) {
   __shared__ __attribute__((aligned(1024))) char smem[ring_bytes<BM, BN, NS, KM>()];
   int zs, xn, ym, zb;
   tile_coords(xcd_linear(blockIdx.x, total), g.nsplit, tn, tm, zfast, zs, xn, ym, zb);
-  pipe_tile<BM, BN, WM, WN, TA, TB, NS, BF, KS, KM>(g, zb, zs, xn, ym, tn, tm, G, smem);
+  pipe_tile<BM, BN, WM, WN, TA, TB, NS, BF, KM>(g, zb, zs, xn, ym, tn, tm, G, smem);
 }
 
-// Grouped launch: up to GROUP_MAX independent problems (any of the four layouts, a runtime switch) in one
-// grid; problem p owns the logical blocks [start[p], start[p + 1]) of the XCD-ordered grid (slices of a
-// tile fastest); no in-launch combine (the group's split-K slabs go to one grouped reduce).
-struct PipeGroup {
-  int n;
-  int start[GROUP_MAX + 1];
-  int tn[GROUP_MAX], tm[GROUP_MAX], variant[GROUP_MAX];   // variant = 4 BF + 2 TA + TB
-  GemmArgs g[GROUP_MAX];
-};
-
-// KS = 2: fp32 problems only (the host launches a group holding a bf16 problem with KS = 1).
-template <int BM, int BN, int WM, int WN, int NS, int KS = 1, int KM = 1>
-__global__ __launch_bounds__(64 * WM * WN * KS) void gemm_pipe_group(PipeGroup P, unsigned total) {
+// Grouped launch: up to GROUP_MAX independent problems (any of the four layouts, fp32 or bf16: a runtime
+// switch on variant = 4 BF + 2 TA + TB) in one grid; problem p owns the logical blocks [start[p], start[p + 1])
+// of the XCD-ordered grid (slices of a tile fastest); no in-launch combine (the group's split-K slabs go to
+// one grouped reduce).
+template <int BM, int BN, int WM, int WN, int NS, int KM = 1>
+__global__ __launch_bounds__(64 * WM * WN) void gemm_pipe_group(GemmGroup P, unsigned total) {
   __shared__ __attribute__((aligned(1024))) char smem[ring_bytes<BM, BN, NS, KM>()];
   const unsigned lin = xcd_linear(blockIdx.x, total);
-  int p = 0;
-#pragma unroll
-  for (int k = 1; k < GROUP_MAX; ++k)
-    if (k < P.n && (int)lin >= P.start[k]) p = k;
-  // the selected problem's descriptor by constant indices only (scalar loads from the argument segment)
-  GemmArgs g = P.g[0];
-  int tn = P.tn[0], tm = P.tm[0], variant = P.variant[0], start = P.start[0];
-#pragma unroll
-  for (int k = 1; k < GROUP_MAX; ++k)
-    if (k == p) {
-      g = P.g[k];
-      tn = P.tn[k];
-      tm = P.tm[k];
-      variant = P.variant[k];
-      start = P.start[k];
-    }
+  const int p = group_owner<GROUP_MAX>(P.n, P.start, (int)lin);
+  const GemmArgs g = group_pick(P.g, p);
+  const int tn = group_pick(P.tn, p), tm = group_pick(P.tm, p);
   int zs, xn, ym, zb;
-  tile_coords(lin - (unsigned)start, g.nsplit, tn, tm, 1, zs, xn, ym, zb);
-  switch (variant) {   // 4 BF + 2 TA + TB
-    case 0: pipe_tile<BM, BN, WM, WN, false, false, NS, false, KS, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
-    case 1: pipe_tile<BM, BN, WM, WN, false, true, NS, false, KS, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
-    case 2: pipe_tile<BM, BN, WM, WN, true, false, NS, false, KS, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
-    case 3: pipe_tile<BM, BN, WM, WN, true, true, NS, false, KS, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
-    default:
-      if constexpr (KS == 1) {
-        switch (variant) {
-          case 4: pipe_tile<BM, BN, WM, WN, false, false, NS, true, 1, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
-          case 5: pipe_tile<BM, BN, WM, WN, false, true, NS, true, 1, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
-          case 6: pipe_tile<BM, BN, WM, WN, true, false, NS, true, 1, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
-          default: pipe_tile<BM, BN, WM, WN, true, true, NS, true, 1, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
-        }
-      }
-      break;
+  tile_coords(lin - (unsigned)group_pick(P.start, p), g.nsplit, tn, tm, 1, zs, xn, ym, zb);
+  switch (group_pick(P.variant, p)) {   // 4 BF + 2 TA + TB
+    case 0: pipe_tile<BM, BN, WM, WN, false, false, NS, false, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
+    case 1: pipe_tile<BM, BN, WM, WN, false, true, NS, false, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
+    case 2: pipe_tile<BM, BN, WM, WN, true, false, NS, false, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
+    case 3: pipe_tile<BM, BN, WM, WN, true, true, NS, false, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
+    case 4: pipe_tile<BM, BN, WM, WN, false, false, NS, true, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
+    case 5: pipe_tile<BM, BN, WM, WN, false, true, NS, true, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
+    case 6: pipe_tile<BM, BN, WM, WN, true, false, NS, true, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
+    default: pipe_tile<BM, BN, WM, WN, true, true, NS, true, KM>(g, zb, zs, xn, ym, tn, tm, 1, smem); break;
   }
 }
 
@@ -980,10 +913,8 @@ struct ReduceGroup {
 __global__ __launch_bounds__(256) void splitk_reduce_sum_group(ReduceGroup R) {
   __shared__ float sh[1024];
   const int b = blockIdx.x;
-  int p = 0;
-#pragma unroll
-  for (int k = 1; k < RGROUP_MAX; ++k)
-    if (k < R.n && b >= R.start[k]) p = k;
+  const int p = group_owner<RGROUP_MAX>(R.n, R.start, b);
+  // (one select over all fields instead of a group_pick per field: 15 VGPRs fewer in this kernel)
   GemmArgs g = R.g[0];
   int G = R.G[0], start = R.start[0];
   long nelem = R.nelem[0];
@@ -1000,7 +931,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_sum_group(ReduceGroup R) {
 
 }  // namespace gp
 
-
+// ------------------------------------------------------------------------------------------------
+// Host side: one problem descriptor (GemmCall), a plan and a launcher per kernel, the grouped launches,
+// the router (gemm_impl) and the C ABI.
+//
 // C[b] = alpha * op(A[b]) * op(B[b]) + beta * C[b] (+ bias[n]) (+ addend[(m % add_mod), n]) (relu);
 // bias_grad (optional): bias_grad[m] = alpha * sum_k op(A)(m,k) + beta * bias_grad[m]
 // tuning override (vc_gemm_tune): 0 / -1 fields = automatic choice
@@ -1025,15 +959,103 @@ VC_EXPORT int vc_gemm_tune(int bm, int bn, int nsplit, int pf, int combine) {
   return VC_OK;
 }
 
+// K split into nsplit slices of k_chunk (the last one may be shorter)
+struct Split {
+  int nsplit, k_chunk;
+};
+
+// `want` slices in whole k-tiles of kt: the slice length, and the slices that are then not empty
+static Split split_k(int K, int want, int kt) {
+  if (want <= 1) return Split{1, vc_cdiv(K, kt) * kt};
+  const int k_chunk = vc_cdiv(vc_cdiv(K, want), kt) * kt;
+  return Split{vc_cdiv(K, k_chunk), k_chunk};
+}
+
+// One problem: the arguments of vc_gemm_ex, in the ABI's order (include/vitcnn.h).  Built once per entry
+// point; the router, the planners and the launchers read it.
+struct GemmCall {
+  int transA, transB, M, N, K;
+  float alpha;
+  const float* A;
+  long lda, strideA;
+  const float* B;
+  long ldb, strideB;
+  float beta;
+  float* C;
+  long ldc, strideC;
+  int batch;
+  const float* bias;
+  const float* addend;
+  long add_ld;
+  int add_mod, flags;
+  float* bias_grad;
+  float* ws;
+  long ws_floats;
+  unsigned int* tile_counters;
+  int n_counters;
+
+  bool bf16() const { return (flags & F_BF16) != 0; }
+  int Ne() const { return N + (bias_grad ? 1 : 0); }   // with the implicit ones column (bias gradient)
+  // the kernels' descriptor of this problem under a split; cnt: the in-launch combine's counters or null
+  GemmArgs args(Split s, unsigned int* cnt) const {
+    const Epi epi{alpha, beta, bias, addend, add_ld, add_mod > 0 ? add_mod : M, flags};
+    return GemmArgs{M, N, K, Ne(), s.k_chunk, s.nsplit, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias_grad, ws,
+                    cnt, epi};
+  }
+  // vector staging (float4 along the contiguous axis): 16-B aligned base, ld % 4, batch stride % 4
+  bool vec(const float* p, long ld, long stride) const {
+    return ((uintptr_t)p % 16 == 0) && (ld % 4 == 0) && (batch == 1 || stride % 4 == 0);
+  }
+  bool vec_a() const { return vec(A, lda, strideA); }
+  bool vec_b() const { return vec(B, ldb, strideB); }
+  // the most slices (<= want) whose slabs [nsplit][batch][M][Ne] fit the workspace
+  int fit_workspace(int want) const {
+    while (want > 1 && (long)want * batch * M * Ne() > ws_floats) --want;
+    return want;
+  }
+  // The in-launch combine's arrival counters, or null = slabs for the separate reduce kernel.  The combine
+  // needs a counter per output tile and pays only while the last arriver's serial slab read stays small:
+  // at most `limit` bytes of slabs per bm x bn tile.
+  unsigned int* combine_counters(int nsplit, int bm, int bn, long tiles, long limit) const {
+    const long slab_bytes = (long)nsplit * std::min(bm, M) * std::min(bn, Ne()) * 4;
+    return (nsplit > 1 && tile_counters && tiles <= n_counters && slab_bytes <= limit) ? tile_counters : nullptr;
+  }
+};
+
 // largest per-tile slab volume (bytes) combined in-launch by the last-arriving slice (else a separate
-// reduce kernel); knob SPLITK_COMBINE (probe library)
-static long g2_combine_limit() { return vc_knob("VITCNN_SPLITK_COMBINE", 4096); }
+// reduce kernel); knob SPLITK_COMBINE (probe library); vc_gemm_tune's `combine` forces either path
+static long g2_combine_limit() {
+  if (g_tune.combine >= 0) return g_tune.combine == 1 ? (1L << 62) : -1;
+  return vc_knob("VITCNN_SPLITK_COMBINE", 4096);
+}
 
 // largest per-tile slab volume (bytes) the k-major kernel's last-arriving slice combines in-launch;
 // knob LEGACY_COMBINE (probe library)
 static long legacy_combine_limit() { return vc_knob("VITCNN_LEGACY_COMBINE", 4096); }
 
-// the k-major fp32 kernel (LDS [k][row], 16x16x4 f32): launch configuration of one problem
+// the separate split-K reduce over the slabs of g (g.nsplit > 1, no arrival counters)
+static int launch_reduce(const GemmArgs& g, int batch, hipStream_t stream) {
+  const long nelem = (long)batch * g.M * g.Ne;
+  const int G = slab_groups(g.nsplit);
+  VC_REQUIRE(nelem < (1L << 31));
+  hipLaunchKernelGGL(g2::splitk_reduce4, dim3(vc_cdiv(nelem, 1024 / G)), dim3(256), 0, stream, g, nelem, G);
+  VC_CHECK_LAUNCH();
+  return VC_OK;
+}
+
+// Run-time booleans to template arguments: calls f(std::bool_constant<b>{}...), so a generic lambda picks
+// the kernel instantiation (transA / transB, vector staging, ...) without a hand-written if chain.
+template <class F>
+static void dispatch_bools(F&& f) {
+  f();
+}
+template <class F, class... Bs>
+static void dispatch_bools(F&& f, bool b, Bs... rest) {
+  if (b) dispatch_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+  else dispatch_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+
+// ---- the k-major fp32 kernel (LDS [k][row], 16x16x4 f32): launch configuration of one problem
 struct LegacyPlan {
   GemmArgs g;
   int tn, tm, nz, variant;
@@ -1042,103 +1064,59 @@ struct LegacyPlan {
   int counters;       // arrival counters used (in-launch combine)
 };
 
-static LegacyPlan plan_legacy(int transA, int transB, int M, int N, int K, float alpha,
-                              const float* A, long lda, long strideA, const float* B, long ldb, long strideB,
-                              float beta, float* C, long ldc, long strideC, int batch,
-                              const float* bias, const float* addend, long add_ld, int add_mod, int flags,
-                              float* bias_grad, float* ws, long ws_floats, unsigned int* tile_counters,
-                              int n_counters) {
-  Epi epi{alpha, beta, bias, addend, add_ld, add_mod > 0 ? add_mod : M, flags};
-  const int Ne = N + (bias_grad ? 1 : 0);
-  const int tn = vc_cdiv(Ne, BN), tm = vc_cdiv(M, BM);
-  const long tiles = (long)tn * tm * batch;
+static LegacyPlan plan_legacy(const GemmCall& c) {
+  const int Ne = c.Ne();
+  const int tn = vc_cdiv(Ne, BN), tm = vc_cdiv(c.M, BM);
+  const long tiles = (long)tn * tm * c.batch;
   // Split K when the output grid leaves the chip short of ~3 blocks per CU (768 blocks): each
   // K slice keeps >= 128 of K (4 BK steps), the slabs must fit the workspace, and the slices are
   // summed in fixed order (slab_sum) so results do not depend on the split's scheduling.
   int nsplit = 1;
   constexpr long kTargetBlocks = 768;
-  if (ws && K >= 256 && tiles < kTargetBlocks / 2) {
+  if (c.ws && c.K >= 256 && tiles < kTargetBlocks / 2) {
     const long want = (kTargetBlocks + tiles - 1) / tiles;
-    const long maxk = K / 128;
-    nsplit = (int)std::min<long>(std::min<long>(want, maxk), 256);
-    while (nsplit > 1 && (long)nsplit * batch * M * Ne > ws_floats) --nsplit;
-    if (nsplit < 1) nsplit = 1;
+    const long maxk = c.K / 128;
+    nsplit = c.fit_workspace((int)std::min<long>(std::min<long>(want, maxk), 256));
   }
-  int k_chunk = K;
-  if (nsplit > 1) {
-    k_chunk = vc_cdiv(vc_cdiv(K, nsplit), BK) * BK;
-    nsplit = vc_cdiv(K, k_chunk);
-  }
+  const Split s = split_k(c.K, nsplit, BK);
   // the in-launch combine pays only while the last arriver's serial slab read stays small
   // (<= 4 KB of slabs per tile, measured: tools/gemm_census.py); wider splits keep the parallel
   // reduce kernel
-  const long slab_bytes = (long)nsplit * std::min(BM, M) * std::min(BN, Ne) * 4;
-  unsigned int* cnt = (nsplit > 1 && tile_counters && tiles <= n_counters && slab_bytes <= legacy_combine_limit())
-                          ? tile_counters
-                          : nullptr;
+  unsigned int* cnt = c.combine_counters(s.nsplit, BM, BN, tiles, legacy_combine_limit());
   LegacyPlan pl;
-  pl.g = GemmArgs{M, N, K, Ne, k_chunk, nsplit, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias_grad, ws, cnt,
-                  epi};
+  pl.g = c.args(s, cnt);
   pl.tn = tn;
   pl.tm = tm;
-  pl.nz = batch * nsplit;
-  const bool va = ((uintptr_t)A % 16 == 0) && (lda % 4 == 0) && (batch == 1 || strideA % 4 == 0);
-  const bool vb = ((uintptr_t)B % 16 == 0) && (ldb % 4 == 0) && (batch == 1 || strideB % 4 == 0);
-  pl.variant = (transA ? 8 : 0) | (transB ? 4 : 0) | (va ? 2 : 0) | (vb ? 1 : 0);
-  pl.reduce = nsplit > 1 && !cnt;
-  pl.ws_floats = nsplit > 1 ? (long)nsplit * batch * M * Ne : 0;
+  pl.nz = c.batch * s.nsplit;
+  pl.variant = (c.transA ? 8 : 0) | (c.transB ? 4 : 0) | (c.vec_a() ? 2 : 0) | (c.vec_b() ? 1 : 0);
+  pl.reduce = s.nsplit > 1 && !cnt;
+  pl.ws_floats = s.nsplit > 1 ? (long)s.nsplit * c.batch * c.M * Ne : 0;
   pl.counters = cnt ? (int)tiles : 0;
   return pl;
 }
 
-// register sets of staged k-tiles in the k-major kernel: 1.  Deeper sets (bit-identical results) measured
-// slower on the whole step -- PD 1 / 2 / 3 / 4: 2.148 / 2.19 / 2.19 / 2.245 ms (round 3,
-// tools/ab_env.sh, profiles/r03_ab_gemm_pd.log): the extra VGPRs cost more occupancy than the earlier
-// loads save latency.  Knob GEMM_PD=2 (probe library) selects the two-set build for measurements.
-static int legacy_pd() { return (int)std::max(1L, std::min(2L, vc_knob("VITCNN_GEMM_PD", 1))); }
-
-template <int PD>
-static int launch_plan_pd(const LegacyPlan& pl, hipStream_t stream) {
-  const GemmArgs& g = pl.g;
-  dim3 grid(pl.tn, pl.tm, pl.nz), block(256);
-#define VC_L(V_, TA_, TB_, VA_, VB_) \
-  case V_: hipLaunchKernelGGL((gemm_f32_mfma<TA_, TB_, VA_, VB_, PD>), grid, block, 0, stream, g); break;
-  switch (pl.variant) {
-    VC_L(0, false, false, false, false) VC_L(1, false, false, false, true)
-    VC_L(2, false, false, true, false) VC_L(3, false, false, true, true)
-    VC_L(4, false, true, false, false) VC_L(5, false, true, false, true)
-    VC_L(6, false, true, true, false) VC_L(7, false, true, true, true)
-    VC_L(8, true, false, false, false) VC_L(9, true, false, false, true)
-    VC_L(10, true, false, true, false) VC_L(11, true, false, true, true)
-    VC_L(12, true, true, false, false) VC_L(13, true, true, false, true)
-    VC_L(14, true, true, true, false) VC_L(15, true, true, true, true)
-    default: return VC_EINVAL;
-  }
-#undef VC_L
-  VC_CHECK_LAUNCH();
-  if (pl.reduce) {
-    const long nelem = (long)(pl.nz / g.nsplit) * g.M * g.Ne;
-    const int G = g2::slab_groups(g.nsplit);
-    VC_REQUIRE(nelem < (1L << 31));
-    hipLaunchKernelGGL(g2::splitk_reduce4, dim3(vc_cdiv(nelem, 1024 / G)), dim3(256), 0, stream, g, nelem, G);
-    VC_CHECK_LAUNCH();
-  }
-  return VC_OK;
-}
-
 static int launch_plan(const LegacyPlan& pl, hipStream_t stream) {
-  return legacy_pd() == 2 ? launch_plan_pd<2>(pl, stream) : launch_plan_pd<1>(pl, stream);
+  const GemmArgs& g = pl.g;
+  const int v = pl.variant;   // 8 TA + 4 TB + 2 VA + VB
+  dispatch_bools(
+      [&](auto TA, auto TB, auto VA, auto VB) {
+        hipLaunchKernelGGL((gemm_f32_mfma<decltype(TA)::value, decltype(TB)::value, decltype(VA)::value, decltype(VB)::value>), dim3(pl.tn, pl.tm, pl.nz), dim3(256),
+                           0, stream, g);
+      },
+      (v & 8) != 0, (v & 4) != 0, (v & 2) != 0, (v & 1) != 0);
+  VC_CHECK_LAUNCH();
+  return pl.reduce ? launch_reduce(g, pl.nz / g.nsplit, stream) : VC_OK;
 }
 
 // ---- gemm_pipe launch configuration
 // Can the pipelined kernel take this problem?  fp32, one batch, 16-B aligned operands with leading
 // dimensions divisible by 4 and K % 4 == 0 (whole 16-B chunks along k), operands < 2 GB (32-bit buffer
 // offsets), the bias-gradient ones column only on a row-contiguous B.
-static bool pipe_fits(int transA, int transB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
-                      int batch, const float* bias_grad) {
-  if (batch != 1 || K % 4 || lda % 4 || ldb % 4 || ((uintptr_t)A % 16) || ((uintptr_t)B % 16)) return false;
-  if (bias_grad && transB) return false;
-  const long ab = (transA ? (long)K * lda : (long)M * lda) * 4, bb = (transB ? (long)N * ldb : (long)K * ldb) * 4;
+static bool pipe_fits(const GemmCall& c) {
+  if (c.batch != 1 || c.K % 4 || c.lda % 4 || c.ldb % 4 || ((uintptr_t)c.A % 16) || ((uintptr_t)c.B % 16)) return false;
+  if (c.bias_grad && c.transB) return false;
+  const long ab = (c.transA ? (long)c.K * c.lda : (long)c.M * c.lda) * 4;
+  const long bb = (c.transB ? (long)c.N * c.ldb : (long)c.K * c.ldb) * 4;
   return ab < (1L << 31) && bb < (1L << 31);
 }
 
@@ -1146,7 +1124,8 @@ static bool pipe_fits(int transA, int transB, int M, int N, int K, const float* 
 // pipeline fills, and (round 5) the small ones of the step with K <= 4096 and an output of >= 2048 elements --
 // the NonLocal / hsi2 products of 1600 rows, 2-3 us faster each than on the k-major kernel; the long-K skinny
 // weight gradients (K = 10 B L rows, M or N < 64) stay on the k-major kernel, which was faster there
-static bool pipe_wanted(int M, int N, int K) {
+static bool pipe_wanted(const GemmCall& c) {
+  const int M = c.M, N = c.N, K = c.K;
   if (!vc_knob("VITCNN_GEMM_PIPE", 1)) return false;
   if ((long)M * N * K >= (1L << 24) && K >= 128 && M >= 128 && N >= 64) return true;
   return vc_knob("VITCNN_GEMM_PIPE_SMALL", 1) && K <= 4096 && M >= 16 && N >= 16 && (long)M * N >= 2048;
@@ -1156,45 +1135,27 @@ struct PipePlan {
   int bm, bn, ns, nsplit, k_chunk, tn, tm;
 };
 
-// bf16 64 x 64 tiles on 8 waves (2 x 4 of 32 x 16: two waves per SIMD, half the DMA pieces per wave) instead of 4
-// (knob: probe library)
-static int pipe_bf_w8() { return vc_knob("VITCNN_PIPE_BF_W8", 1) ? 1 : 0; }
-// the same for fp32 tiles: equal or 1-5 % faster on every shape of the step, step 1.714 -> 1.690 ms
-// (profiles/r05_gemm_f32_w8.log; knob: probe library)
-static int pipe_f32_w8() { return vc_knob("VITCNN_PIPE_F32_W8", 1) ? 1 : 0; }
-// k-tiles per ring stage of the 8-wave 64 x 64 kernels (pipe_tile KM; knob: probe library)
-static int pipe_km() { return vc_knob("VITCNN_PIPE_KM", 1) == 2 ? 2 : 1; }
-
-// k-split waves (gp::pipe_tile KS = 2) for fp32 64 x 64 tiles.  Rule 0: where the grid is at most one block per CU
-// and K is long (the local 3x3 convs, M = B 49, K = 9 C: 34.1 -> 31.8 us; elsewhere equal or slower,
-// profiles/r05_gemm_ks.log).  Superseded by the 8-wave 2 x 4 layout (pipe_f32_w8: 32.1 us on the local conv and
-// faster elsewhere), so the default is 1 = never.  Knob (probe library): 0 = the rule, 1 = never, 2 = always.
-static int pipe_ks(long tiles = 0, int nsplit = 1, int K = 0) {
-  const int k = vc_knob("VITCNN_PIPE_KS", 1);
-  if (k) return k == 2 ? 2 : 1;
-  return (nsplit == 1 && tiles > 0 && tiles <= 256 && K >= 1024) ? 2 : 1;
-}
-
 // Launch plan (tools/gemm_lab.hip sweep over the step's 21 critical-path shapes, profiles/r04_gemm_lab.log):
 // 64 x 64 tiles on 4 waves with a 2-stage ring (32 KB: up to 5 blocks per CU) won or tied on nearly every
 // shape; a grid of >= 128 tiles runs unsplit (the split-K slab reduce costs more than the extra blocks
 // gain), a smaller one splits K towards ~512 blocks in slices of >= 4 k-tiles (the weight gradients,
 // K = 1600-5184 rows over a 2 x 5 ... 4 x 21 tile grid).
-static PipePlan plan_pipe(int M, int Ne, int K, long ws_floats, bool have_ws, bool bf = false) {
+static PipePlan plan_pipe(const GemmCall& c) {
+  const int K = c.K;
   PipePlan p;
   p.bm = 64;
   p.bn = 64;
   p.ns = vc_knob("VITCNN_PIPE_NS", 2) == 4 ? 4 : 2;   // ring depth (knob: probe library)
   if (g_tune.bm) p.bm = g_tune.bm;
   if (g_tune.bn) p.bn = g_tune.bn;
-  if (bf && p.bm == 128 && p.bn == 128) p.bn = 64;   // (no 128 x 128 build)
-  p.tn = vc_cdiv(Ne, p.bn);
-  p.tm = vc_cdiv(M, p.bm);
+  if (c.bf16() && p.bm == 128 && p.bn == 128) p.bn = 64;   // (no 128 x 128 build)
+  p.tn = vc_cdiv(c.Ne(), p.bn);
+  p.tm = vc_cdiv(c.M, p.bm);
   const long tiles = (long)p.tn * p.tm;
   const int kt = vc_cdiv(K, gp::KT);
   int nsplit = 1;
   const long target = vc_knob("VITCNN_PIPE_SPLIT_BLOCKS", 512);   // blocks a split aims at (knob: probe library)
-  if (have_ws && tiles < vc_knob("VITCNN_PIPE_SPLIT_BELOW", 128)) {   // (knob: probe library)
+  if (c.ws && tiles < vc_knob("VITCNN_PIPE_SPLIT_BELOW", 128)) {   // (knob: probe library)
     const int cap = (int)std::max<long>(1, std::min<long>(kt / 4, 64));
     const int n0 = (int)std::max<long>(1, std::min<long>((target + tiles - 1) / tiles, cap));
     nsplit = n0;
@@ -1206,8 +1167,7 @@ static PipePlan plan_pipe(int M, int Ne, int K, long ws_floats, bool have_ws, bo
       constexpr long NCU = 256;
       double best = -1.0;
       for (int n = n0; n <= std::min(2 * n0, cap); ++n) {
-        const int kc = vc_cdiv(vc_cdiv(K, n), gp::KT) * gp::KT;
-        const long blocks = tiles * vc_cdiv(K, kc);
+        const long blocks = tiles * split_k(K, n, gp::KT).nsplit;
         const double fill = (double)blocks / (double)(vc_cdiv(blocks, NCU) * NCU);
         if (fill > best + 1e-9) {
           best = fill;
@@ -1217,89 +1177,152 @@ static PipePlan plan_pipe(int M, int Ne, int K, long ws_floats, bool have_ws, bo
     }
   }
   if (g_tune.nsplit) nsplit = std::min(g_tune.nsplit, std::max(1, kt));
-  while (nsplit > 1 && (long)nsplit * M * Ne > ws_floats) --nsplit;
-  p.k_chunk = kt * gp::KT;
-  if (nsplit > 1) {
-    p.k_chunk = vc_cdiv(vc_cdiv(K, nsplit), gp::KT) * gp::KT;
-    nsplit = vc_cdiv(K, p.k_chunk);
-  }
-  p.nsplit = nsplit;
+  const Split s = split_k(K, c.fit_workspace(nsplit), gp::KT);
+  p.nsplit = s.nsplit;
+  p.k_chunk = s.k_chunk;
   return p;
 }
 
-static int launch_pipe(int transA, int transB, int M, int N, int K, float alpha, const float* A, long lda,
-                       const float* B, long ldb, float beta, float* C, long ldc, const float* bias,
-                       const float* addend, long add_ld, int add_mod, int flags, float* bias_grad, float* ws,
-                       long ws_floats, unsigned int* tile_counters, int n_counters, hipStream_t stream) {
-  Epi epi{alpha, beta, bias, addend, add_ld, add_mod > 0 ? add_mod : M, flags};
-  const int Ne = N + (bias_grad ? 1 : 0);
-  const bool bf = (flags & F_BF16) != 0;
-  const PipePlan p = plan_pipe(M, Ne, K, ws_floats, ws != nullptr, bf);
+// bf16 64 x 64 tiles on 8 waves (2 x 4 of 32 x 16: two waves per SIMD, half the DMA pieces per wave) instead of 4
+// (knob: probe library)
+static int pipe_bf_w8() { return vc_knob("VITCNN_PIPE_BF_W8", 1) ? 1 : 0; }
+// the same for fp32 tiles: equal or 1-5 % faster on every shape of the step, step 1.714 -> 1.690 ms
+// (profiles/r05_gemm_f32_w8.log; knob: probe library)
+static int pipe_f32_w8() { return vc_knob("VITCNN_PIPE_F32_W8", 1) ? 1 : 0; }
+// k-tiles per ring stage of the 8-wave 64 x 64 kernels (pipe_tile KM; knob: probe library)
+static int pipe_km() { return vc_knob("VITCNN_PIPE_KM", 1) == 2 ? 2 : 1; }
+
+// The pipelined kernel's shape: BM x BN tile on WM x WN waves, NS ring stages of KM k-tiles.  One choice
+// for the single launch, the grouped launch and vc_gemm_colstats.  Tiles other than 64 x 64 and rings other
+// than 2 stages are measurement settings (probe library); a bf16 ring of 4 stages exists for the 4-wave
+// 64 x 64 tile only.
+struct PipeShape {
+  int bm, bn, wm, wn, ns, km;
+};
+
+static PipeShape pipe_shape(int bm, int bn, int ns, bool bf) {
+  if (bm == 128 && bn == 64) return PipeShape{128, 64, 4, 2, bf ? 2 : ns, 1};
+  if (bm == 64 && bn == 128) return PipeShape{64, 128, 2, 4, bf ? 2 : ns, 1};
+  if (bf && ns == 4) return PipeShape{64, 64, 2, 2, 4, 1};
+  if (bf ? pipe_bf_w8() : pipe_f32_w8()) return PipeShape{64, 64, 2, 4, ns, pipe_km()};
+  return PipeShape{64, 64, 2, 2, ns, 1};
+}
+
+// A built shape as a type, and the lists of built shapes: pipe_dispatch calls f(PipeKernel<...>{}) for the
+// one that `s` names (false: not in the list).
+template <int BM_, int BN_, int WM_, int WN_, int NS_, int KM_>
+struct PipeKernel {
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, NS = NS_, KM = KM_;
+  static bool is(const PipeShape& s) {
+    return s.bm == BM && s.bn == BN && s.wm == WM && s.wn == WN && s.ns == NS && s.km == KM;
+  }
+};
+template <class... Ks>
+struct PipeKernels {};
+// 64 x 64 tiles with a 2-stage ring: all the grouped launch and vc_gemm_colstats take
+typedef PipeKernels<PipeKernel<64, 64, 2, 4, 2, 1>, PipeKernel<64, 64, 2, 4, 2, 2>, PipeKernel<64, 64, 2, 2, 2, 1>>
+    PipeKernels64;
+typedef PipeKernels<PipeKernel<64, 64, 2, 4, 2, 1>, PipeKernel<64, 64, 2, 4, 2, 2>, PipeKernel<64, 64, 2, 2, 2, 1>,
+                    PipeKernel<64, 64, 2, 2, 4, 1>, PipeKernel<128, 64, 4, 2, 2, 1>, PipeKernel<64, 128, 2, 4, 2, 1>>
+    PipeKernelsBf16;
+typedef PipeKernels<PipeKernel<64, 64, 2, 4, 2, 1>, PipeKernel<64, 64, 2, 4, 2, 2>, PipeKernel<64, 64, 2, 2, 2, 1>,
+                    PipeKernel<64, 64, 2, 2, 4, 1>, PipeKernel<128, 64, 4, 2, 2, 1>, PipeKernel<64, 128, 2, 4, 2, 1>,
+                    PipeKernel<64, 64, 2, 4, 4, 1>, PipeKernel<64, 64, 2, 4, 4, 2>, PipeKernel<128, 64, 4, 2, 4, 1>,
+                    PipeKernel<64, 128, 2, 4, 4, 1>>
+    PipeKernelsF32;
+
+template <class F, class... Ks>
+static bool pipe_dispatch(const PipeShape& s, PipeKernels<Ks...>, F&& f) {
+  return ((Ks::is(s) && (f(Ks{}), true)) || ...);
+}
+
+static int launch_pipe(const GemmCall& c, const PipePlan& p, hipStream_t stream) {
   const long tiles = (long)p.tn * p.tm;
-  const long slab_bytes = (long)p.nsplit * std::min(p.bm, M) * std::min(p.bn, Ne) * 4;
-  bool inl = slab_bytes <= g2_combine_limit();
-  if (g_tune.combine >= 0) inl = g_tune.combine == 1;
-  unsigned int* cnt = (p.nsplit > 1 && tile_counters && tiles <= n_counters && inl) ? tile_counters : nullptr;
-  GemmArgs g{M, N, K, Ne, p.k_chunk, p.nsplit, A, lda, 0, B, ldb, 0, C, ldc, 0, bias_grad, ws, cnt, epi};
+  unsigned int* cnt = c.combine_counters(p.nsplit, p.bm, p.bn, tiles, g2_combine_limit());
+  const GemmArgs g = c.args(Split{p.nsplit, p.k_chunk}, cnt);
   const long total = tiles * p.nsplit;
   VC_REQUIRE(total < (1L << 31));
-  const int G = g2::slab_groups(p.nsplit);
+  const int G = slab_groups(p.nsplit);
   // split slice fastest in the block order: a tile's K slices run side by side on one XCD (measured
   // faster for every split shape of the step, tools/gemm_lab.hip; the in-launch combine reads its slabs there)
   const int zfast = 1;
-  dim3 grid((unsigned)total);
-#define VC_GP(BM_, BN_, WM_, WN_, NS_, KS_, KM_)                                                                \
-  do {                                                                                                           \
-    const dim3 blk(64 * WM_ * WN_ * KS_);                                                                        \
-    if (transA && transB)                                                                                        \
-      hipLaunchKernelGGL((gp::gemm_pipe<BM_, BN_, WM_, WN_, true, true, NS_, false, KS_, KM_>), grid, blk, 0, stream, g, p.tn, p.tm, (unsigned)total, G, zfast);   \
-    else if (transA)                                                                                             \
-      hipLaunchKernelGGL((gp::gemm_pipe<BM_, BN_, WM_, WN_, true, false, NS_, false, KS_, KM_>), grid, blk, 0, stream, g, p.tn, p.tm, (unsigned)total, G, zfast);  \
-    else if (transB)                                                                                             \
-      hipLaunchKernelGGL((gp::gemm_pipe<BM_, BN_, WM_, WN_, false, true, NS_, false, KS_, KM_>), grid, blk, 0, stream, g, p.tn, p.tm, (unsigned)total, G, zfast);  \
-    else                                                                                                         \
-      hipLaunchKernelGGL((gp::gemm_pipe<BM_, BN_, WM_, WN_, false, false, NS_, false, KS_, KM_>), grid, blk, 0, stream, g, p.tn, p.tm, (unsigned)total, G, zfast); \
-  } while (0)
-#define VC_GP_T(NS_)                                                \
-  do {                                                              \
-    if (p.bm == 128 && p.bn == 64) VC_GP(128, 64, 4, 2, NS_, 1, 1);     \
-    else if (p.bm == 64 && p.bn == 128) VC_GP(64, 128, 2, 4, NS_, 1, 1); \
-    else if (pipe_ks(tiles, p.nsplit, K) == 2) VC_GP(64, 64, 2, 2, NS_, 2, 1); \
-    else if (pipe_f32_w8() && km == 2) VC_GP(64, 64, 2, 4, NS_, 1, 2);  \
-    else if (pipe_f32_w8()) VC_GP(64, 64, 2, 4, NS_, 1, 1);            \
-    else VC_GP(64, 64, 2, 2, NS_, 1, 1);                               \
-  } while (0)
-#define VC_GPB(BM_, BN_, WM_, WN_, TA_, TB_, NS_, KM_) \
-  hipLaunchKernelGGL((gp::gemm_pipe<BM_, BN_, WM_, WN_, TA_, TB_, NS_, true, 1, KM_>), grid, dim3(64 * WM_ * WN_), 0, stream, g, p.tn, p.tm, (unsigned)total, G, zfast)
-#define VC_GPB_L(BM_, BN_, WM_, WN_, NS_, KM_)                          \
-  do {                                                                  \
-    if (transA && transB) VC_GPB(BM_, BN_, WM_, WN_, true, true, NS_, KM_); \
-    else if (transA) VC_GPB(BM_, BN_, WM_, WN_, true, false, NS_, KM_);     \
-    else if (transB) VC_GPB(BM_, BN_, WM_, WN_, false, true, NS_, KM_);     \
-    else VC_GPB(BM_, BN_, WM_, WN_, false, false, NS_, KM_);                \
-  } while (0)
-  const int km = pipe_km();
-  if (bf) {   // tiles other than 64 x 64 / 2 stages: measurement knobs (probe library)
-    if (p.bm == 128 && p.bn == 64) VC_GPB_L(128, 64, 4, 2, 2, 1);
-    else if (p.bm == 64 && p.bn == 128) VC_GPB_L(64, 128, 2, 4, 2, 1);
-    else if (p.ns == 4) VC_GPB_L(64, 64, 2, 2, 4, 1);
-    else if (pipe_bf_w8() && km == 2) VC_GPB_L(64, 64, 2, 4, 2, 2);
-    else if (pipe_bf_w8()) VC_GPB_L(64, 64, 2, 4, 2, 1);
-    else VC_GPB_L(64, 64, 2, 2, 2, 1);
-  } else if (p.ns == 4) VC_GP_T(4);
-  else VC_GP_T(2);
-#undef VC_GPB_L
-#undef VC_GPB
-#undef VC_GP_T
-#undef VC_GP
+  auto launch = [&](auto BF, auto k) {
+    using Kn = decltype(k);
+    dispatch_bools(
+        [&](auto TA, auto TB) {
+          hipLaunchKernelGGL((gp::gemm_pipe<Kn::BM, Kn::BN, Kn::WM, Kn::WN, decltype(TA)::value, decltype(TB)::value, Kn::NS, decltype(BF)::value, Kn::KM>),
+                             dim3((unsigned)total), dim3(64 * Kn::WM * Kn::WN), 0, stream, g, p.tn, p.tm, (unsigned)total,
+                             G, zfast);
+        },
+        c.transA != 0, c.transB != 0);
+  };
+  const PipeShape s = pipe_shape(p.bm, p.bn, p.ns, c.bf16());
+  VC_REQUIRE(c.bf16() ? pipe_dispatch(s, PipeKernelsBf16{}, [&](auto k) { launch(std::true_type{}, k); })
+                      : pipe_dispatch(s, PipeKernelsF32{}, [&](auto k) { launch(std::false_type{}, k); }));
   VC_CHECK_LAUNCH();
-  if (p.nsplit > 1 && !cnt) {
-    const long nelem = (long)M * Ne;
-    VC_REQUIRE(nelem < (1L << 31));
-    hipLaunchKernelGGL(g2::splitk_reduce4, dim3(vc_cdiv(nelem, 1024 / G)), dim3(256), 0, stream, g, nelem, G);
-    VC_CHECK_LAUNCH();
+  return (p.nsplit > 1 && !cnt) ? launch_reduce(g, 1, stream) : VC_OK;
+}
+
+// ---- the K-contiguous kernel (g2::gemm_mfma), fp32 or bf16: launch configuration of one problem
+struct G2Plan {
+  GemmArgs g;
+  int bm, bn, tn, tm, pf;
+  long total;   // blocks
+};
+
+// Configuration from the sweep of the step's shapes (tools/gemm_sweep.py):
+//  * 64 x 64 tiles; bf16 takes 128-row tiles for grids of >= 1024 tiles (fewer B re-reads);
+//  * split K when the grid is small (< 192 tiles) or K is long (>= 1024): slices of >= 2 k-tiles,
+//    up to ~4 blocks per CU (1024 blocks), at most 256 slices; the weight gradients (K = rows,
+//    tiny grids) end at 64-256 slices of 2-3 k-tiles each;
+//  * two k-tiles of loads in flight (pf 2) for bf16 weight gradients, else one.
+static G2Plan plan_g2(const GemmCall& c) {
+  const bool bf = c.bf16();
+  const int M = c.M, K = c.K, Ne = c.Ne();
+  const int KT = bf ? 64 : 32;
+  const int tiles64 = vc_cdiv(Ne, 64) * vc_cdiv(M, 64) * c.batch;
+  G2Plan pl;
+  pl.bm = (bf && tiles64 >= 1024) ? 128 : 64;
+  pl.bn = 64;
+  if (g_tune.bm) pl.bm = g_tune.bm;
+  if (g_tune.bn) pl.bn = g_tune.bn;
+  pl.tn = vc_cdiv(Ne, pl.bn);
+  pl.tm = vc_cdiv(M, pl.bm);
+  const long tiles = (long)pl.tn * pl.tm * c.batch;
+  int nsplit = 1;
+  if (K >= 4 * KT && (tiles < 192 || K >= 1024)) {
+    const long by_k = K / (2 * KT);
+    const long by_blocks = std::max<long>(1, 1024 / tiles);
+    nsplit = (int)std::min<long>(std::min<long>(by_k, by_blocks), 256);
   }
-  return VC_OK;
+  if (!bf) nsplit = std::max(nsplit, vc_cdiv(K, 2048));  // fp32: slices of <= 2048 (accuracy)
+  if (g_tune.nsplit) nsplit = std::min(g_tune.nsplit, std::max(1, K / KT));
+  if (!c.ws) nsplit = 1;
+  const Split s = split_k(K, c.fit_workspace(nsplit), KT);
+  pl.pf = g_tune.pf ? g_tune.pf : ((bf && c.transA) ? 2 : 1);
+  // the slices of a tile run side by side on one XCD (split index fastest in the block order), so
+  // the last arriver's slab reads are L2 hits: combine in-launch unless the tile's slabs are large
+  pl.g = c.args(s, c.combine_counters(s.nsplit, pl.bm, pl.bn, tiles, g2_combine_limit()));
+  pl.total = tiles * s.nsplit;
+  return pl;
+}
+
+static int launch_g2(const GemmCall& c, const G2Plan& pl, hipStream_t stream) {
+  const GemmArgs& g = pl.g;
+  VC_REQUIRE(pl.total < (1L << 31));
+  const int va = c.vec_a(), vb = c.vec_b();
+  const int G = slab_groups(g.nsplit);
+  const int zfast = g.cnt ? 1 : 0;
+  dispatch_bools(
+      [&](auto BF, auto PF2, auto M128, auto N128, auto TA, auto TB) {
+        hipLaunchKernelGGL((g2::gemm_mfma<decltype(BF)::value, decltype(M128)::value ? 128 : 64, decltype(N128)::value ? 128 : 64, decltype(TA)::value, decltype(TB)::value,
+                                          decltype(PF2)::value ? 2 : 1>),
+                           dim3((unsigned)pl.total), dim3(256), 0, stream, g, pl.tn, pl.tm, (unsigned)pl.total, va, vb, G,
+                           zfast);
+      },
+      c.bf16(), pl.pf == 2, pl.bm == 128, pl.bn == 128, c.transA != 0, c.transB != 0);
+  VC_CHECK_LAUNCH();
+  return (g.nsplit > 1 && !g.cnt) ? launch_reduce(g, c.batch, stream) : VC_OK;
 }
 
 // ---- grouped launches: the problems added to a group (vc_gemm_group_add) launch at vc_gemm_group_end as
@@ -1310,7 +1333,7 @@ static int launch_pipe(int transA, int transB, int M, int N, int K, float alpha,
 // library keeps none and distinct groups are independent.
 struct PipeRec {
   GemmArgs g;
-  int tn, tm, variant;   // variant = 2 transA + transB
+  int tn, tm, variant;   // variant = 4 bf16 + 2 transA + transB
 };
 
 struct GroupState {
@@ -1329,7 +1352,8 @@ static_assert(sizeof(GroupState) <= VC_GEMM_GROUP_BYTES, "VC_GEMM_GROUP_BYTES to
 struct ReduceItems {
   gp::ReduceGroup R;
   long total = 0;
-  void add(const GemmArgs& g, int G, int batch) {
+  void add(const GemmArgs& g, int batch) {
+    const int G = slab_groups(g.nsplit);
     R.start[R.n] = (int)total;
     R.g[R.n] = g;
     R.G[R.n] = G;
@@ -1338,6 +1362,16 @@ struct ReduceItems {
     total += (R.nelem[R.n - 1] + 1024 / G - 1) / (1024 / G);
   }
 };
+
+// problem p of a grouped grid: its first block and its descriptor; returns the first block after it
+static long group_put(GemmGroup& G, int p, long start, int tn, int tm, int variant, const GemmArgs& g, long blocks) {
+  G.start[p] = (int)start;
+  G.tn[p] = tn;
+  G.tm[p] = tm;
+  G.variant[p] = variant;
+  G.g[p] = g;
+  return start + blocks;
+}
 
 static int group_flush(GroupState& st) {
   const int n = st.n, np = st.np;
@@ -1355,57 +1389,40 @@ static int group_flush(GroupState& st) {
     pl.reduce = false;
     const int rc = launch_plan(pl, st.stream);
     if (rc) return rc;
-    if (reduce) red.add(pl.g, g2::slab_groups(pl.g.nsplit), pl.nz / pl.g.nsplit);
+    if (reduce) red.add(pl.g, pl.nz / pl.g.nsplit);
   } else if (n > 1) {
     GemmGroup G;
     G.n = n;
     long total = 0;
     for (int p = 0; p < n; ++p) {
       const LegacyPlan& pl = st.plans[p];
-      G.start[p] = (int)total;
-      G.tn[p] = pl.tn;
-      G.tm[p] = pl.tm;
-      G.variant[p] = pl.variant;
-      G.g[p] = pl.g;
-      total += (long)pl.tn * pl.tm * pl.nz;
-      if (pl.reduce) red.add(pl.g, g2::slab_groups(pl.g.nsplit), pl.nz / pl.g.nsplit);
+      total = group_put(G, p, total, pl.tn, pl.tm, pl.variant, pl.g, (long)pl.tn * pl.tm * pl.nz);
+      if (pl.reduce) red.add(pl.g, pl.nz / pl.g.nsplit);
     }
     G.start[n] = (int)total;
     VC_REQUIRE(total < (1L << 31));
-    if (legacy_pd() == 2) hipLaunchKernelGGL(gemm_f32_group<2>, dim3((unsigned)total), dim3(256), 0, st.stream, G);
-    else hipLaunchKernelGGL(gemm_f32_group<1>, dim3((unsigned)total), dim3(256), 0, st.stream, G);
+    hipLaunchKernelGGL(gemm_f32_group, dim3((unsigned)total), dim3(256), 0, st.stream, G);
     VC_CHECK_LAUNCH();
   }
   if (np > 0) {
-    gp::PipeGroup P;
+    GemmGroup P;
     P.n = np;
     long total = 0;
+    bool any_bf = false;
     for (int p = 0; p < np; ++p) {
       const PipeRec& pr = st.pipes[p];
-      P.start[p] = (int)total;
-      P.tn[p] = pr.tn;
-      P.tm[p] = pr.tm;
-      P.variant[p] = pr.variant;
-      P.g[p] = pr.g;
-      total += (long)pr.tn * pr.tm * pr.g.nsplit;
-      if (pr.g.nsplit > 1) red.add(pr.g, g2::slab_groups(pr.g.nsplit), 1);
+      total = group_put(P, p, total, pr.tn, pr.tm, pr.variant, pr.g, (long)pr.tn * pr.tm * pr.g.nsplit);
+      if (pr.g.nsplit > 1) red.add(pr.g, 1);
+      any_bf |= pr.variant >= 4;
     }
     P.start[np] = (int)total;
     VC_REQUIRE(total < (1L << 31));
-    bool any_bf = false;
-    for (int p = 0; p < np; ++p) any_bf |= st.pipes[p].variant >= 4;
-    if (!any_bf && vc_knob("VITCNN_PIPE_KS", 0) == 2)   // (grouped problems: measured no gain)
-      hipLaunchKernelGGL((gp::gemm_pipe_group<64, 64, 2, 2, 2, 2>), dim3((unsigned)total), dim3(512), 0, st.stream, P,
-                         (unsigned)total);
-    else if (((any_bf && pipe_bf_w8()) || (!any_bf && pipe_f32_w8())) && pipe_km() == 2)   // 8 waves, 2 k-tiles
-      hipLaunchKernelGGL((gp::gemm_pipe_group<64, 64, 2, 4, 2, 1, 2>), dim3((unsigned)total), dim3(512), 0, st.stream,
-                         P, (unsigned)total);
-    else if ((any_bf && pipe_bf_w8()) || (!any_bf && pipe_f32_w8()))   // 8 waves of 32 x 16
-      hipLaunchKernelGGL((gp::gemm_pipe_group<64, 64, 2, 4, 2>), dim3((unsigned)total), dim3(512), 0, st.stream, P,
-                         (unsigned)total);
-    else
-      hipLaunchKernelGGL((gp::gemm_pipe_group<64, 64, 2, 2, 2>), dim3((unsigned)total), dim3(256), 0, st.stream, P,
-                         (unsigned)total);
+    // one shape for the whole grid: the bf16 choice if any problem of the group has bf16 operands
+    VC_REQUIRE(pipe_dispatch(pipe_shape(64, 64, 2, any_bf), PipeKernels64{}, [&](auto k) {
+      using Kn = decltype(k);
+      hipLaunchKernelGGL((gp::gemm_pipe_group<Kn::BM, Kn::BN, Kn::WM, Kn::WN, Kn::NS, Kn::KM>), dim3((unsigned)total),
+                         dim3(64 * Kn::WM * Kn::WN), 0, st.stream, P, (unsigned)total);
+    }));
     VC_CHECK_LAUNCH();
   }
   if (red.R.n) {
@@ -1416,6 +1433,73 @@ static int group_flush(GroupState& st) {
     VC_CHECK_LAUNCH();
   }
   return VC_OK;
+}
+
+// A k-major problem joins the group.  Its plan (split-K slices, combine path) depends on the problem and
+// the caller's whole workspace / counter arrays only -- never on what a group has used of them -- so a GEMM
+// gives the same bits grouped or alone, whatever its neighbours (tests/test_model_gpu.py::test_lane_schedules_*)
+static int group_add_legacy(GroupState& st, const GemmCall& c, LegacyPlan pl) {
+  const long need = (pl.ws_floats + 63) / 64 * 64;
+  if (st.n == GROUP_MAX || st.ws_used + need > c.ws_floats || st.cnt_used + pl.counters > c.n_counters) {
+    const int rc = group_flush(st);   // launch what is recorded; this problem starts a new group
+    if (rc) return rc;
+  }
+  // this problem's slices of the workspace and the counters follow the earlier problems' slices
+  if (pl.g.nsplit > 1) pl.g.part = c.ws + st.ws_used;
+  if (pl.g.cnt) pl.g.cnt = c.tile_counters + st.cnt_used;
+  st.ws_used += need;
+  st.cnt_used += pl.counters;
+  st.plans[st.n++] = pl;
+  return VC_OK;
+}
+
+// A pipelined problem joins the group: its own slice of the workspace, no in-launch combine (no counters)
+static int group_add_pipe(GroupState& st, const GemmCall& c, const PipePlan& p) {
+  const long need = p.nsplit > 1 ? ((long)p.nsplit * c.M * c.Ne() + 63) / 64 * 64 : 0;
+  if (st.np == GROUP_MAX || st.ws_used + need > c.ws_floats) {
+    const int rc = group_flush(st);
+    if (rc) return rc;
+  }
+  PipeRec& pr = st.pipes[st.np++];
+  pr.g = c.args(Split{p.nsplit, p.k_chunk}, nullptr);
+  if (p.nsplit > 1) pr.g.part = c.ws + st.ws_used;
+  pr.tn = p.tn;
+  pr.tm = p.tm;
+  pr.variant = (c.bf16() ? 4 : 0) | (c.transA ? 2 : 0) | (c.transB ? 1 : 0);
+  st.ws_used += need;
+  return VC_OK;
+}
+
+// ---- the router: which kernel takes the problem.  group: the open group of vc_gemm_group_add, or null
+static int gemm_impl(const GemmCall& c, hipStream_t stream, GroupState* group) {
+  VC_REQUIRE(c.M >= 0 && c.N >= 0 && c.K >= 0 && c.batch >= 1);
+  VC_REQUIRE(!c.bias_grad || c.batch == 1);
+  if (c.M == 0 || c.N == 0) return VC_OK;
+  const int flags = c.flags;
+  // mid shapes: the LDS-DMA pipelined kernel, fp32 or (F_BF16) bf16 MFMAs over the same fp32 stages
+  // (F_PIPE forces it where it fits, F_NOPIPE keeps the older kernels: tests, census).  The choice depends on
+  // the problem only: a grouped problem that takes it joins the group's pipelined grid or, as below,
+  // launches at once on the group's stream
+  if (!(flags & (F_LEGACY | F_V2 | F_NOPIPE)) && pipe_fits(c) && ((flags & F_PIPE) || pipe_wanted(c))) {
+    const PipePlan p = plan_pipe(c);
+    // a problem whose own grid fills the chip launches alone (knob GEMM_GROUP_MAXB: the largest grid
+    // that joins a group; probe library), as do the tiles and rings the grouped kernel is not built for
+    const long own = (long)p.tn * p.tm * p.nsplit;
+    if (group && p.bm == 64 && p.bn == 64 && p.ns == 2 && own <= vc_knob("VITCNN_GEMM_GROUP_MAXB", 1L << 30))
+      return group_add_pipe(*group, c, p);
+    return launch_pipe(c, p, stream);
+  }
+  // fp32: the k-major kernel (faster on every shape of the ViT-CNN step, tools/gemm_census.py) except
+  // long contractions (K >= 4096, e.g. FusAtNet's 3x3 convs over 1024-2193 channels), where the
+  // K-contiguous kernel's two accumulator chains and <= 2048-long slices keep the fp32 rounding at
+  // the CPU reference's level (tools/gemm_err.py).  F_LEGACY / F_V2 force either (tests, census).
+  const bool legacy = !c.bf16() && !(flags & F_V2) && ((flags & F_LEGACY) || c.K < 4096 || c.transA);
+  if (legacy) {
+    const LegacyPlan pl = plan_legacy(c);
+    return group ? group_add_legacy(*group, c, pl) : launch_plan(pl, stream);
+  }
+  // the K-contiguous kernel launches at once, grouped or not
+  return launch_g2(c, plan_g2(c), stream);
 }
 
 static GroupState* group_of(void* group) {
@@ -1444,42 +1528,9 @@ VC_EXPORT int vc_gemm_group_end(void* group) {
   return err ? err : rc;
 }
 
-static int launch_legacy(int transA, int transB, int M, int N, int K, float alpha,
-                         const float* A, long lda, long strideA, const float* B, long ldb, long strideB,
-                         float beta, float* C, long ldc, long strideC, int batch,
-                         const float* bias, const float* addend, long add_ld, int add_mod, int flags,
-                         float* bias_grad, float* ws, long ws_floats, unsigned int* tile_counters,
-                         int n_counters, hipStream_t stream, GroupState* st) {
-  // the plan (split-K slices, combine path) depends on the problem and the caller's whole workspace /
-  // counter arrays only -- never on what a group has used of them -- so a GEMM gives the same bits
-  // grouped or alone, whatever its neighbours (tests/test_model_gpu.py::test_lane_schedules_*)
-  LegacyPlan pl = plan_legacy(transA, transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC,
-                              batch, bias, addend, add_ld, add_mod, flags, bias_grad, ws, ws_floats, tile_counters,
-                              n_counters);
-  if (!st) return launch_plan(pl, stream);
-  const long need = (pl.ws_floats + 63) / 64 * 64;
-  if (st->n == GROUP_MAX || st->ws_used + need > ws_floats || st->cnt_used + pl.counters > n_counters) {
-    const int rc = group_flush(*st);   // launch what is recorded; this problem starts a new group
-    if (rc) return rc;
-  }
-  // this problem's slices of the workspace and the counters follow the earlier problems' slices
-  if (pl.g.nsplit > 1) pl.g.part = ws + st->ws_used;
-  if (pl.g.cnt) pl.g.cnt = tile_counters + st->cnt_used;
-  st->ws_used += need;
-  st->cnt_used += pl.counters;
-  st->plans[st->n++] = pl;
-  return VC_OK;
-}
-
-static int gemm_impl(int transA, int transB, int M, int N, int K, float alpha,
-                     const float* A, long lda, long strideA, const float* B, long ldb, long strideB,
-                     float beta, float* C, long ldc, long strideC, int batch,
-                     const float* bias, const float* addend, long add_ld, int add_mod, int flags,
-                     float* bias_grad, float* ws, long ws_floats, unsigned int* tile_counters,
-                     int n_counters, hipStream_t stream, GroupState* group);
-
-// a problem of the group: the fp32 k-major ones wait for vc_gemm_group_end; any other (bf16 operands,
-// K >= 4096) launches at once on the group's stream
+// a problem of the group: the fp32 k-major ones and the pipelined ones that fit the grouped kernel wait for
+// vc_gemm_group_end; any other (K-contiguous kernel: K >= 4096 or bf16 off the pipelined kernel) launches at
+// once on the group's stream
 VC_EXPORT int vc_gemm_group_add(void* group, int transA, int transB, int M, int N, int K, float alpha,
                                 const float* A, long lda, long strideA, const float* B, long ldb, long strideB,
                                 float beta, float* C, long ldc, long strideC, int batch,
@@ -1488,9 +1539,9 @@ VC_EXPORT int vc_gemm_group_add(void* group, int transA, int transB, int M, int 
                                 int n_counters) {
   GroupState* st = group_of(group);
   VC_REQUIRE(st && st->magic == GROUP_MAGIC);
-  const int rc = gemm_impl(transA, transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC,
-                           batch, bias, addend, add_ld, add_mod, flags, bias_grad, ws, ws_floats, tile_counters,
-                           n_counters, st->stream, st);
+  const GemmCall c{transA, transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch,
+                   bias, addend, add_ld, add_mod, flags, bias_grad, ws, ws_floats, tile_counters, n_counters};
+  const int rc = gemm_impl(c, st->stream, st);
   if (rc && !st->err) st->err = rc;
   return rc;
 }
@@ -1501,32 +1552,26 @@ VC_EXPORT int vc_gemm_group_add(void* group, int transA, int transB, int M, int 
 VC_EXPORT int vc_gemm_colstats(int M, int N, int K, const float* A, long lda, const float* W, long ldw,
                                const float* bias, float* C, long ldc, int flags, double* colstats, hipStream_t stream) {
   VC_REQUIRE(M > 0 && N > 0 && K > 0 && bias && colstats);
-  VC_REQUIRE(pipe_fits(0, 1, M, N, K, A, lda, W, ldw, 1, nullptr));
-  const bool bf = (flags & F_BF16) != 0;
-  PipePlan p = plan_pipe(M, N, K, 0, false, bf);   // no workspace: no split
+  // (no workspace: no split)
+  const GemmCall c{0, 1, M, N, K, 1.f, A, lda, 0, W, ldw, 0, 0.f, C, ldc, 0, 1,
+                   bias, nullptr, 0, 0, flags & F_BF16, nullptr, nullptr, 0, nullptr, 0};
+  VC_REQUIRE(pipe_fits(c));
+  const PipePlan p = plan_pipe(c);
   VC_REQUIRE(p.nsplit == 1 && p.bm == 64 && p.bn == 64 && p.ns == 2);
-  Epi epi{1.f, 0.f, bias, nullptr, 0, M, 0};
-  GemmArgs g{M, N, K, N, p.k_chunk, 1, A, lda, 0, W, ldw, 0, C, ldc, 0, nullptr, nullptr, nullptr, epi};
+  GemmArgs g = c.args(Split{1, p.k_chunk}, nullptr);
   g.colstats = colstats;
   g.shift = bias;
   const long total = (long)p.tn * p.tm;
-  dim3 grid((unsigned)total);
-  if (bf) {
-    if (pipe_bf_w8())
-      hipLaunchKernelGGL((gp::gemm_pipe<64, 64, 2, 4, false, true, 2, true>), grid, dim3(512), 0, stream, g, p.tn,
-                         p.tm, (unsigned)total, 1, 1);
-    else
-      hipLaunchKernelGGL((gp::gemm_pipe<64, 64, 2, 2, false, true, 2, true>), grid, dim3(256), 0, stream, g, p.tn,
-                         p.tm, (unsigned)total, 1, 1);
-  } else if (pipe_ks(total, 1, K) == 2)
-    hipLaunchKernelGGL((gp::gemm_pipe<64, 64, 2, 2, false, true, 2, false, 2>), grid, dim3(512), 0, stream, g, p.tn,
-                       p.tm, (unsigned)total, 1, 1);
-  else if (pipe_f32_w8())
-    hipLaunchKernelGGL((gp::gemm_pipe<64, 64, 2, 4, false, true, 2>), grid, dim3(512), 0, stream, g, p.tn, p.tm,
-                       (unsigned)total, 1, 1);
-  else
-    hipLaunchKernelGGL((gp::gemm_pipe<64, 64, 2, 2, false, true, 2>), grid, dim3(256), 0, stream, g, p.tn, p.tm,
-                       (unsigned)total, 1, 1);
+  VC_REQUIRE(pipe_dispatch(pipe_shape(p.bm, p.bn, p.ns, c.bf16()), PipeKernels64{}, [&](auto k) {
+    using Kn = decltype(k);
+    dispatch_bools(
+        [&](auto BF) {
+          hipLaunchKernelGGL((gp::gemm_pipe<Kn::BM, Kn::BN, Kn::WM, Kn::WN, false, true, Kn::NS, decltype(BF)::value, Kn::KM>),
+                             dim3((unsigned)total), dim3(64 * Kn::WM * Kn::WN), 0, stream, g, p.tn, p.tm, (unsigned)total,
+                             1, 1);
+        },
+        c.bf16());
+  }));
   VC_CHECK_LAUNCH();
   return VC_OK;
 }
@@ -1537,149 +1582,9 @@ VC_EXPORT int vc_gemm_ex(int transA, int transB, int M, int N, int K, float alph
                          const float* bias, const float* addend, long add_ld, int add_mod, int flags,
                          float* bias_grad, float* ws, long ws_floats, unsigned int* tile_counters,
                          int n_counters, hipStream_t stream) {
-  return gemm_impl(transA, transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch,
-                   bias, addend, add_ld, add_mod, flags, bias_grad, ws, ws_floats, tile_counters, n_counters, stream,
-                   nullptr);
-}
-
-static int gemm_impl(int transA, int transB, int M, int N, int K, float alpha,
-                     const float* A, long lda, long strideA, const float* B, long ldb, long strideB,
-                     float beta, float* C, long ldc, long strideC, int batch,
-                     const float* bias, const float* addend, long add_ld, int add_mod, int flags,
-                     float* bias_grad, float* ws, long ws_floats, unsigned int* tile_counters,
-                     int n_counters, hipStream_t stream, GroupState* group) {
-  VC_REQUIRE(M >= 0 && N >= 0 && K >= 0 && batch >= 1);
-  VC_REQUIRE(!bias_grad || batch == 1);
-  if (M == 0 || N == 0) return VC_OK;
-  const bool bf = (flags & F_BF16) != 0;
-  // mid shapes: the LDS-DMA pipelined kernel, fp32 or (F_BF16) bf16 MFMAs over the same fp32 stages
-  // (F_PIPE forces it where it fits, F_NOPIPE keeps the older kernels: tests, census).  The choice depends on the problem only: a grouped problem that
-  // takes it launches at once on the group's stream
-  if (!(flags & (F_LEGACY | F_V2 | F_NOPIPE)) &&
-      pipe_fits(transA, transB, M, N, K, A, lda, B, ldb, batch, bias_grad) &&
-      ((flags & F_PIPE) || pipe_wanted(M, N, K))) {
-    const int fl = flags & ~(F_PIPE | F_NOPIPE);
-    const int Ne = N + (bias_grad ? 1 : 0);
-    const PipePlan p = plan_pipe(M, Ne, K, ws_floats, ws != nullptr, bf);
-    if (group) {
-      // a problem whose own grid fills the chip launches alone (knob GEMM_GROUP_MAXB: the largest grid
-      // that joins a group; probe library)
-      const long own = (long)p.tn * p.tm * p.nsplit;
-      if (p.bm == 64 && p.bn == 64 && p.ns == 2 && own <= vc_knob("VITCNN_GEMM_GROUP_MAXB", 1L << 30)) {
-        const long need = p.nsplit > 1 ? ((long)p.nsplit * M * Ne + 63) / 64 * 64 : 0;
-        GroupState& st = *group;
-        if (st.np == GROUP_MAX || st.ws_used + need > ws_floats) {
-          const int rc = group_flush(st);
-          if (rc) return rc;
-        }
-        Epi epi{alpha, beta, bias, addend, add_ld, add_mod > 0 ? add_mod : M, fl};
-        PipeRec& pr = st.pipes[st.np++];
-        pr.g = GemmArgs{M, N, K, Ne, p.k_chunk, p.nsplit, A, lda, 0, B, ldb, 0, C, ldc, 0, bias_grad,
-                        p.nsplit > 1 ? ws + st.ws_used : ws, nullptr, epi};
-        pr.tn = p.tn;
-        pr.tm = p.tm;
-        pr.variant = (bf ? 4 : 0) | (transA ? 2 : 0) | (transB ? 1 : 0);
-        st.ws_used += need;
-        return VC_OK;
-      }
-    }
-    return launch_pipe(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, addend, add_ld, add_mod,
-                       fl, bias_grad, ws, ws_floats, tile_counters, n_counters, stream);
-  }
-  // fp32: the k-major kernel (faster on every shape of the ViT-CNN step, tools/gemm_census.py) except
-  // long contractions (K >= 4096, e.g. FusAtNet's 3x3 convs over 1024-2193 channels), where the
-  // K-contiguous kernel's two accumulator chains and <= 2048-long slices keep the fp32 rounding at
-  // the CPU reference's level (tools/gemm_err.py).  F_LEGACY / F_V2 force either (tests, census).
-  const bool legacy = !bf && !(flags & F_V2) && ((flags & F_LEGACY) || K < 4096 || transA);
-  if (legacy)
-    return launch_legacy(transA, transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC,
-                         batch, bias, addend, add_ld, add_mod, flags, bias_grad, ws, ws_floats, tile_counters,
-                         n_counters, stream, group);
-  Epi epi{alpha, beta, bias, addend, add_ld, add_mod > 0 ? add_mod : M, flags};
-  const int Ne = N + (bias_grad ? 1 : 0);
-  const int KT = bf ? 64 : 32;
-  // Configuration from the sweep of the step's shapes (tools/gemm_sweep.py):
-  //  * 64 x 64 tiles; bf16 takes 128-row tiles for grids of >= 1024 tiles (fewer B re-reads);
-  //  * split K when the grid is small (< 192 tiles) or K is long (>= 1024): slices of >= 2 k-tiles,
-  //    up to ~4 blocks per CU (1024 blocks), at most 256 slices; the weight gradients (K = rows,
-  //    tiny grids) end at 64-256 slices of 2-3 k-tiles each;
-  //  * two k-tiles of loads in flight (pf 2) for bf16 weight gradients, else one.
-  const int tiles64 = vc_cdiv(Ne, 64) * vc_cdiv(M, 64) * batch;
-  int BM = (bf && tiles64 >= 1024) ? 128 : 64;
-  int BN = 64;
-  if (g_tune.bm) BM = g_tune.bm;
-  if (g_tune.bn) BN = g_tune.bn;
-  const int tn = vc_cdiv(Ne, BN), tm = vc_cdiv(M, BM);
-  const long tiles = (long)tn * tm * batch;
-  int nsplit = 1;
-  if (K >= 4 * KT && (tiles < 192 || K >= 1024)) {
-    const long by_k = K / (2 * KT);
-    const long by_blocks = std::max<long>(1, 1024 / tiles);
-    nsplit = (int)std::min<long>(std::min<long>(by_k, by_blocks), 256);
-  }
-  if (!bf) nsplit = std::max(nsplit, vc_cdiv(K, 2048));  // fp32: slices of <= 2048 (accuracy)
-  if (g_tune.nsplit) nsplit = std::min(g_tune.nsplit, std::max(1, K / KT));
-  if (!ws) nsplit = 1;
-  while (nsplit > 1 && (long)nsplit * batch * M * Ne > ws_floats) --nsplit;
-  int k_chunk = vc_cdiv(K, KT) * KT;
-  if (nsplit > 1) {
-    k_chunk = vc_cdiv(vc_cdiv(K, nsplit), KT) * KT;
-    nsplit = vc_cdiv(K, k_chunk);
-  }
-  const int pf = g_tune.pf ? g_tune.pf : ((bf && transA) ? 2 : 1);
-  // the slices of a tile run side by side on one XCD (split index fastest in the block order), so
-  // the last arriver's slab reads are L2 hits: combine in-launch unless the tile's slabs are large
-  const long slab_bytes = (long)nsplit * std::min(BM, M) * std::min(BN, Ne) * 4;
-  bool inl = slab_bytes <= g2_combine_limit();
-  if (g_tune.combine >= 0) inl = g_tune.combine == 1;
-  unsigned int* cnt = (nsplit > 1 && tile_counters && tiles <= n_counters && inl) ? tile_counters : nullptr;
-  GemmArgs g{M, N, K, Ne, k_chunk, nsplit, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias_grad, ws, cnt, epi};
-  const long total = tiles * nsplit;
-  VC_REQUIRE(total < (1L << 31));
-  // vector staging (float4 along the contiguous axis): 16-B aligned base, ld % 4, batch stride % 4
-  auto vec_ok = [&](const float* p, long ld, long stride) {
-    return ((uintptr_t)p % 16 == 0) && (ld % 4 == 0) && (batch == 1 || stride % 4 == 0);
-  };
-  const int va = vec_ok(A, lda, strideA);
-  const int vb = vec_ok(B, ldb, strideB);
-  const int G = g2::slab_groups(nsplit);
-  const int zfast = cnt ? 1 : 0;
-  dim3 grid((unsigned)total), block(256);
-#define VC_G2(BF_, BM_, BN_, PF_)                                                                                 \
-  do {                                                                                                            \
-    if (transA && transB)                                                                                         \
-      hipLaunchKernelGGL((g2::gemm_mfma<BF_, BM_, BN_, true, true, PF_>), grid, block, 0, stream, g, tn, tm, (unsigned)total, va, vb, G, zfast);   \
-    else if (transA)                                                                                              \
-      hipLaunchKernelGGL((g2::gemm_mfma<BF_, BM_, BN_, true, false, PF_>), grid, block, 0, stream, g, tn, tm, (unsigned)total, va, vb, G, zfast);  \
-    else if (transB)                                                                                              \
-      hipLaunchKernelGGL((g2::gemm_mfma<BF_, BM_, BN_, false, true, PF_>), grid, block, 0, stream, g, tn, tm, (unsigned)total, va, vb, G, zfast);  \
-    else                                                                                                          \
-      hipLaunchKernelGGL((g2::gemm_mfma<BF_, BM_, BN_, false, false, PF_>), grid, block, 0, stream, g, tn, tm, (unsigned)total, va, vb, G, zfast); \
-  } while (0)
-#define VC_G2_T(BF_, PF_)                                  \
-  do {                                                     \
-    if (BM == 128 && BN == 128) VC_G2(BF_, 128, 128, PF_); \
-    else if (BM == 128) VC_G2(BF_, 128, 64, PF_);          \
-    else if (BN == 128) VC_G2(BF_, 64, 128, PF_);          \
-    else VC_G2(BF_, 64, 64, PF_);                          \
-  } while (0)
-  if (bf) {
-    if (pf == 2) VC_G2_T(true, 2);
-    else VC_G2_T(true, 1);
-  } else {
-    if (pf == 2) VC_G2_T(false, 2);
-    else VC_G2_T(false, 1);
-  }
-#undef VC_G2_T
-#undef VC_G2
-  VC_CHECK_LAUNCH();
-  if (nsplit > 1 && !cnt) {
-    const long nelem = (long)batch * M * Ne;
-    VC_REQUIRE(nelem < (1L << 31));
-    hipLaunchKernelGGL(g2::splitk_reduce4, dim3(vc_cdiv(nelem, 1024 / G)), dim3(256), 0, stream, g, nelem, G);
-    VC_CHECK_LAUNCH();
-  }
-  return VC_OK;
+  const GemmCall c{transA, transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch,
+                   bias, addend, add_ld, add_mod, flags, bias_grad, ws, ws_floats, tile_counters, n_counters};
+  return gemm_impl(c, stream, nullptr);
 }
 
 VC_EXPORT int vc_gemm(int transA, int transB, int M, int N, int K, float alpha,
