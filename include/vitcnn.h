@@ -577,4 +577,62 @@ VC_API int vc_col2im3x3_pad(int B, int H, int W, int C, int pad, const float* dc
 VC_API int vc_pool_scale_bwd(int B, int HW, int HWp, int C, const float* pooled, const float* F, long ldf,
                              const float* dout, long lddo, float* dF, long lddf, float* dpooled, hipStream_t stream);
 
+/* ---------------------------------------------------------------- MFT (comparison model)
+ * model/compare_method/MFT.py.  All fp32 with fp32 accumulation; the feature width is 64 (FM * 4, FM = 16).
+ *
+ * vc_mft_conv3d_fwd / _wgrad: conv5's Conv3d(1, 8, (9,3,3), padding (0,1,1)) (MFT.py:137) over x [B, NC, P, P]
+ *   (the batch layout; the band axis is the depth), D = NC - 8 output depths, 5 <= P <= 28:
+ *     y[(b*P*P + h*P + w) * ldy + d*8 + c] = bias[c] + sum_{kd<9,kh<3,kw<3} w[c][kd][kh][kw] x[b][d+kd][h+kh-1][w+kw-1]
+ *   i.e. channels-last rows of 8 D channels ordered d*8 + c (ldy >= 8 D, ldy % 4 == 0, y 16-B aligned): the rows
+ *   viewed as [B*P*P*D, 8] are a plain 8-channel BatchNorm (BatchNorm3d(8)) and the 3x3 conv that follows reads
+ *   them as they are.  wgrad: dw [8][81] (= [8,1,9,3,3]) = sum_{b,d,h,w} dy[..., d*8+c] x[b][d+kd][h+kh-1][w+kw-1],
+ *   db[c] = sum dy[..., d*8+c], both overwritten; per-block partials in ws (vc_mft_conv3d_ws_floats), summed
+ *   in a fixed order.  x is data: there is no input gradient.
+ * vc_mft_hetconv_pack / _unpack: conv6's HetConv (MFT.py:15-25) gwc(x) + pwc(x), gwc = Conv2d(C, O, 3, groups g,
+ *   padding 1), pwc = Conv2d(C, O, 1), as ONE dense 3x3 conv in vc_conv3x3_tap_*'s tap-major layout over the
+ *   d*8 + c channel order above (C = 8 D; torch channel ch = c*D + d <-> column k = d*8 + c):
+ *     wt[o][tap][k] = (ch / (C/g) == o / (O/g) ? gwc_w[o][ch % (C/g)][tap] : 0) + (tap == 4 ? pwc_w[o][ch] : 0),
+ *     bias[o] = gwc_b[o] + pwc_b[o];
+ *   unpack: dgwc_w[o][cl][tap] = dwt[o][tap][k(ch = (o/(O/g)) * (C/g) + cl)], dpwc_w[o][ch] = dwt[o][4][k(ch)]
+ *   (entries off the group diagonal are ignored).  C % g == 0, O % g == 0.
+ * vc_mft_tokpool_fwd / _bwd: the tokenisers (MFT.py:187-207) for X [B*HW, 64] rows (ldx), L <= 4 tokens, HW <= 1024:
+ *     A[b,l,:] = softmax_i(sum_j wA[l][j] X[b,i,j]),  U[b,l,j] = sum_i A[b,l,i] X[b,i,j],
+ *     T[b*strideT + l*ldt + k] = sum_j U[b,l,j] wV[j][k] (+ add[l][k], nullable: the position embedding rows)
+ *   ((A X) wV, a reassociation of A (X wV)); A [B,L,HW] and U [B,L,64] are saved.  bwd from dT (same strides):
+ *   dX (lddx, overwritten), dwA [L][64], dwV [64][64] (overwritten; per-sample partials in ws, >= B * (L*64 + 4096)
+ *   floats, summed in a fixed order).
+ * vc_mft_xattn_fwd / _bwd: MCrossAttention's core (MFT.py:42-56), 8 heads over 8-feature slices of Y [B, T, 64]
+ *   (2 <= T <= 16), wq / wk / wv [64][8] applied to every slice: q[b,h,:] = wq Y[b,0,8h:8h+8],
+ *   k / v[b,h,t,:] = wk / wv Y[b,t,8h:8h+8], a = softmax_t(scale q . k_t), O[b][h*64 + e] = sum_t a_t v[b,h,t,e];
+ *   attn [B,8,T] saved.  bwd from dO [B, 512]: dY [B,T,64] (overwritten), dwq / dwk / dwv (overwritten; per-sample
+ *   partials in ws, >= B * 1536 floats, summed over heads and batch in a fixed order: no atomics).
+ * vc_mft_bcast_add_fwd / _bwd: Block's residual x + h with x [B,1,D] broadcast over h [B,T,D] (MFT.py:101):
+ *   out[b,t,:] = h[b,t,:] + a[b,:];  da[b,:] = sum_t dout[b,t,:]. */
+VC_API int vc_mft_conv3d_ws_floats(int B, int NC, int P);
+VC_API int vc_mft_conv3d_fwd(int B, int NC, int P, const float* x, const float* w, const float* bias, float* y, long ldy,
+                             hipStream_t stream);
+VC_API int vc_mft_conv3d_wgrad(int B, int NC, int P, const float* x, const float* dy, long lddy, float* dw, float* db,
+                               float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_mft_hetconv_pack(int O, int C, int g, const float* gwc_w, const float* pwc_w, const float* gwc_b,
+                               const float* pwc_b, float* wt, float* bias, hipStream_t stream);
+VC_API int vc_mft_hetconv_unpack(int O, int C, int g, const float* dwt, float* dgwc_w, float* dpwc_w,
+                                 hipStream_t stream);
+VC_API int vc_mft_tokpool_fwd(int B, int HW, int L, const float* X, long ldx, const float* wA, const float* wV,
+                              const float* add, float* A, float* U, float* T, long ldt, long strideT,
+                              hipStream_t stream);
+VC_API int vc_mft_tokpool_bwd(int B, int HW, int L, const float* X, long ldx, const float* wA, const float* wV,
+                              const float* A, const float* U, const float* dT, long ldt, long strideT, float* dX,
+                              long lddx, float* dwA, float* dwV, float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_mft_xattn_fwd(int B, int T, const float* Y, const float* wq, const float* wk, const float* wv,
+                            float scale, float* O, float* attn, hipStream_t stream);
+VC_API int vc_mft_xattn_bwd(int B, int T, const float* Y, const float* wq, const float* wk, const float* wv,
+                            const float* attn, const float* dO, float scale, float* dY, float* dwq, float* dwk,
+                            float* dwv, float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_mft_bcast_add_fwd(int B, int T, int D, const float* h, const float* a, float* out, hipStream_t stream);
+VC_API int vc_mft_bcast_add_bwd(int B, int T, int D, const float* dout, float* da, hipStream_t stream);
+/* torch.optim.Adam step with coupled L2 weight decay (MFT's optimizer, model_utils.py:364-376) over a flat buffer:
+ * g = grad_scale * grad + weight_decay * p before the moments, then Adam's update; hyper / step as vc_adamw */
+VC_API int vc_adam(long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* hyper,
+                   float* step, hipStream_t stream);
+
 #endif /* VITCNN_H */

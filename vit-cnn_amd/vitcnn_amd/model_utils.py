@@ -10,8 +10,8 @@ replaces, so `main.py`-style drivers switch by changing one import:
 * `test(run, net, img1, img2, hyperparams) -> probs[W, H, n_classes]` — :1067-1132.
 * `val(net, data_loader, device, supervision) -> accuracy` — :1135-1158.
 
-Registered: "Multimodality_Mamba" (the README's "ViT-CNN (ours)"), "S2EFT" (config 5, :400-423) and
-"FusAtNet" (config 5, :109-118).
+Registered: "Multimodality_Mamba" (the README's "ViT-CNN (ours)"), "S2EFT" (config 5, :400-423),
+"FusAtNet" (config 5, :109-118) and "MFT" (:364-376).
 The reference's other branches import modules absent from the reference tree (SURVEY.md section 2a
 row 22) and are out of scope for this path.
 
@@ -41,7 +41,7 @@ from .model import Multimodality_Mamba
 from .optim import AdamW
 from .window import SlidingWindowInference
 
-REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet")
+REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT")
 
 
 def camel_to_snake(name: str) -> str:
@@ -70,6 +70,8 @@ def get_model(name, **kwargs):
         return _get_s2eft(n_bands, n_classes, device, kwargs)
     if name == "FusAtNet":
         return _get_fusatnet(n_bands, n_bands2, n_classes, device, kwargs)
+    if name == "MFT":
+        return _get_mft(n_bands, n_bands2, n_classes, device, kwargs)
     kwargs.setdefault("patch_size", 9)
     patch_size = kwargs["patch_size"]
     center_pixel = True
@@ -134,6 +136,28 @@ def _get_fusatnet(n_bands, n_bands2, n_classes, device, kwargs):
     kwargs.setdefault("epoch", 150)
     kwargs.setdefault("batch_size", 64)
     kwargs.setdefault("applyPCA", False)
+    kwargs.setdefault("supervision", "full")
+    kwargs["center_pixel"] = True
+    return model, optimizer, criterion, kwargs
+
+
+def _get_mft(n_bands, n_bands2, n_classes, device, kwargs):
+    """MFT branch of model_utils.py:364-376: MFT(patch_size, FM 16, NC n_bands (30 under applyPCA), NCLidar n_bands2,
+    HSIOnly False), patch 11, Adam(lr 5e-4, weight_decay 5e-3) -- torch.optim.Adam's coupled L2 decay, the fused
+    `vitcnn_amd.optim.Adam` over the flat buffer --, weighted CE, epoch 500, batch 64."""
+    from .mft import MFT
+    from .optim import Adam
+    kwargs.setdefault("patch_size", 11)
+    kwargs.setdefault("applyPCA", False)
+    if kwargs["applyPCA"]:
+        n_bands = 30
+    model = MFT(patch_size=kwargs["patch_size"], FM=16, NC=n_bands, NCLidar=n_bands2, Classes=n_classes,
+                HSIOnly=False).to(device)
+    lr = kwargs.setdefault("lr", 0.0005)
+    optimizer = Adam(model.parameters(), lr=lr, weight_decay=5e-3)
+    criterion = CrossEntropyLoss(weight=kwargs["weights"])
+    kwargs.setdefault("epoch", 500)
+    kwargs.setdefault("batch_size", 64)
     kwargs.setdefault("supervision", "full")
     kwargs["center_pixel"] = True
     return model, optimizer, criterion, kwargs

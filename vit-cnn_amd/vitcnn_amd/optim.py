@@ -78,6 +78,31 @@ class AdamW(torch.optim.Optimizer):
         self._owner().zero_grad(set_to_none=set_to_none)
 
 
+class Adam(AdamW):
+    """torch.optim.Adam with its coupled L2 weight decay (MFT's optimizer, model_utils.py:373): the decay is added
+    to the gradient before the moments (`g = grad_scale * g + weight_decay * p`, the `vc_adam` kernel) instead of
+    AdamW's decoupled parameter shrink.  Same flat-buffer, device-resident hyper-parameter and step layout as
+    AdamW, so a step replays inside a hipGraph; an AdamW for every check of the optimizer's kind."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        model = self._owner()
+        flat = model.flat_params
+        g = flat.grad
+        if g is None:
+            return loss
+        st = self.sync_hyper()
+        model._grad_views = False   # as AdamW.step: this optimizer reads the flat gradient
+        s = torch.cuda.current_stream(flat.device).cuda_stream
+        lib().vc_adam(model._n_active, flat.data_ptr(), g.data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(),
+                      st["hyper"].data_ptr(), st["step"].data_ptr(), s)
+        return loss
+
+
 def _torch_step_pre_hook(opt, args, kwargs):
     """Global step pre-hook of every torch optimizer: a torch optimizer (e.g. the reference pattern
     torch.optim.Adam(model.parameters())) stepping a flat-buffer vitcnn_amd model needs the per-parameter
