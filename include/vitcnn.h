@@ -635,4 +635,44 @@ VC_API int vc_mft_bcast_add_bwd(int B, int T, int D, const float* dout, float* d
 VC_API int vc_adam(long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* hyper,
                    float* step, hipStream_t stream);
 
+/* ---------------------------------------------------------------- MDL-RS fusion CNNs (comparison models)
+ * model/compare_method/DML_Hong.py (Early / Middle / Late / Cross_fusion_CNN) and losses.py:7-19.  All fp32.
+ *
+ * vc_maxpool2p_fwd / _bwd: nn.MaxPool2d(kernel_size=2, stride=2, padding=1) (DML_Hong.py:18) over a channels-last map
+ *   x [B,H,W,C] (row stride ldx), H, W >= 2: y [B,OH,OW,C] (dense), OH = H/2 + 1, OW = W/2 + 1; output (oh, ow) covers
+ *   rows 2 oh - 1, 2 oh and columns 2 ow - 1, 2 ow, taps outside the map are -inf padding; arg (uint8) = kh * 2 + kw of
+ *   the first maximum among the in-range taps in (kh, kw) order, as torch.  bn_* (all or none, vc_conv3x3_fwd's
+ *   convention): every tap is first mapped through relu((x - mean) * invstd * w + b) with vc_bn_apply's arithmetic,
+ *   so BatchNorm apply, ReLU and pool are one pass over the conv output (y is bit-identical to vc_bn_apply with
+ *   relu = 1 followed by the plain pool; pooling in front of the affine would be wrong for w < 0).
+ *   bwd: dx[b,h,w,c] (ld lddx, overwritten, every element written once) = dy[b,(h+1)/2,(w+1)/2,c] where arg names
+ *   that pixel, 0 elsewhere (the windows do not overlap: a gather); with y (the forward's output, nullable) the ReLU
+ *   mask y > 0 is folded in, and dx is the gradient of the BatchNorm output: it feeds vc_bn_bwd_ex with no relu_out.
+ * vc_avgpool_head_fwd / _bwd: nn.AdaptiveAvgPool2d(1) of G in {1, 2, 3} dense maps f_g [B,HW,C] (C <= 1024) followed
+ *   by conv7, a 1x1 conv on a 1x1 map, as a product.  mode 0 (concat, Late_fusion_CNN's cat[x1, x2], :221):
+ *   pooled [B, G C] with column g C + c, logits [B, ncls] = pooled W^T + bias, W [ncls, G C]; mode 1 (separate,
+ *   Cross_fusion_CNN's three heads, :305-318): pooled [G, B, C], logits [G, B, ncls] = pooled W^T + bias with the one
+ *   W [ncls, C].  pooled is kept for the backward.  bwd from dlogits (the logits' shape): dW, db (overwritten) summed
+ *   over the batch and, in mode 1, over the G applications in a fixed order (no atomics: a second call gives the same
+ *   bits); df_g [B,HW,C] (overwritten) = (dlogits W)[., column] / HW at every pixel.
+ * vc_xfusion_loss_fwd_bwd: Cross_fusion_CNN_Loss for o1, o2, o3 [B, ncls]:
+ *     loss = CE_weight(o1, target) + mean((o1 - o2)^2) + mean((o1 - o3)^2)   (means over all B ncls elements)
+ *   and, for d(loss) = 1, do1 = dCE + 2 (o1 - o2) / n + 2 (o1 - o3) / n, do2 = -2 (o1 - o2) / n, do3 = -2 (o1 - o3) / n,
+ *   n = B ncls, in ONE launch.  target int64 (-100 is ignored, nn.CrossEntropyLoss's default), weight may be null.
+ *   The cross-entropy half is vc_ce_fwd_bwd's code: with o2 = o3 = o1 loss and do1 are its bits, do2 = do3 = 0. */
+VC_API int vc_maxpool2p_fwd(int B, int H, int W, int C, const float* x, long ldx, const float* bn_mean,
+                            const float* bn_invstd, const float* bn_w, const float* bn_b, float* y, unsigned char* arg,
+                            hipStream_t stream);
+VC_API int vc_maxpool2p_bwd(int B, int H, int W, int C, const float* dy, const unsigned char* arg, const float* y,
+                            float* dx, long lddx, hipStream_t stream);
+VC_API int vc_avgpool_head_fwd(int B, int HW, int C, int G, int ncls, int mode, const float* f0, const float* f1,
+                               const float* f2, const float* W, const float* bias, float* pooled, float* logits,
+                               hipStream_t stream);
+VC_API int vc_avgpool_head_bwd(int B, int HW, int C, int G, int ncls, int mode, const float* dlogits, const float* W,
+                               const float* pooled, float* df0, float* df1, float* df2, float* dW, float* db,
+                               hipStream_t stream);
+VC_API int vc_xfusion_loss_fwd_bwd(int B, int ncls, const float* o1, const float* o2, const float* o3,
+                                   const long long* target, const float* weight, float* loss, float* do1, float* do2,
+                                   float* do3, hipStream_t stream);
+
 #endif /* VITCNN_H */

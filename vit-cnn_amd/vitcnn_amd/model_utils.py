@@ -11,7 +11,9 @@ replaces, so `main.py`-style drivers switch by changing one import:
 * `val(net, data_loader, device, supervision) -> accuracy` — :1135-1158.
 
 Registered: "Multimodality_Mamba" (the README's "ViT-CNN (ours)"), "S2EFT" (config 5, :400-423),
-"FusAtNet" (config 5, :109-118) and "MFT" (:364-376).
+"FusAtNet" (config 5, :109-118), "MFT" (:364-376) and the four MDL-RS baselines "Early_fusion_CNN",
+"Middle_fusion_CNN", "Late_fusion_CNN" and "Cross_fusion_CNN" (:69-108; the last trains with
+`Cross_fusion_CNN_Loss` over its three outputs, and `val` / `test` read the first).
 The reference's other branches import modules absent from the reference tree (SURVEY.md section 2a
 row 22) and are out of scope for this path.
 
@@ -41,7 +43,8 @@ from .model import Multimodality_Mamba
 from .optim import AdamW
 from .window import SlidingWindowInference
 
-REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT")
+MDLRS = ("Early_fusion_CNN", "Middle_fusion_CNN", "Late_fusion_CNN", "Cross_fusion_CNN")
+REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT") + MDLRS
 
 
 def camel_to_snake(name: str) -> str:
@@ -72,6 +75,8 @@ def get_model(name, **kwargs):
         return _get_fusatnet(n_bands, n_bands2, n_classes, device, kwargs)
     if name == "MFT":
         return _get_mft(n_bands, n_bands2, n_classes, device, kwargs)
+    if name in MDLRS:
+        return _get_mdlrs(name, n_bands, n_bands2, n_classes, device, kwargs)
     kwargs.setdefault("patch_size", 9)
     patch_size = kwargs["patch_size"]
     center_pixel = True
@@ -158,6 +163,29 @@ def _get_mft(n_bands, n_bands2, n_classes, device, kwargs):
     criterion = CrossEntropyLoss(weight=kwargs["weights"])
     kwargs.setdefault("epoch", 500)
     kwargs.setdefault("batch_size", 64)
+    kwargs.setdefault("supervision", "full")
+    kwargs["center_pixel"] = True
+    return model, optimizer, criterion, kwargs
+
+
+def _get_mdlrs(name, n_bands, n_bands2, n_classes, device, kwargs):
+    """The four MDL-RS branches of model_utils.py:69-108, which differ in the class and the criterion only:
+    <name>(n_bands, n_bands2, n_classes), patch 7, Adam(lr 1e-3) -- the fused AdamW kernel with weight_decay 0, as
+    FusAtNet --, weighted CE (Cross_fusion_CNN: Cross_fusion_CNN_Loss(weight)), epoch 150, batch 64, applyPCA False
+    (it does not change n_bands here, as in the reference)."""
+    from . import mdlrs
+    from .losses import Cross_fusion_CNN_Loss
+    kwargs.setdefault("patch_size", 7)
+    model = getattr(mdlrs, name)(n_bands, n_bands2, n_classes, patch_size=kwargs["patch_size"]).to(device)
+    lr = kwargs.setdefault("lr", 0.001)
+    optimizer = AdamW(model.parameters(), lr=lr, weight_decay=0.0)
+    if name == "Cross_fusion_CNN":
+        criterion = Cross_fusion_CNN_Loss(weight=kwargs["weights"])
+    else:
+        criterion = CrossEntropyLoss(weight=kwargs["weights"])
+    kwargs.setdefault("epoch", 150)
+    kwargs.setdefault("batch_size", 64)
+    kwargs.setdefault("applyPCA", False)
     kwargs.setdefault("supervision", "full")
     kwargs["center_pixel"] = True
     return model, optimizer, criterion, kwargs
