@@ -1,6 +1,6 @@
 """Guards that need no GPU: every entry point of include/vitcnn.h is named by some test, and the S2EFT /
-FusAtNet / glue entry points, LayerNorm, vc_gemm and the Mamba scan refuse invalid arguments on the host, before
-any launch."""
+FusAtNet / glue entry points, LayerNorm, vc_gemm, the Mamba scan, the 3x3 convolutions, the max pool, the non-local
+attention, the row chains and the TokenLearner refuse invalid arguments on the host, before any launch."""
 import glob
 import os
 import re
@@ -59,6 +59,39 @@ REJECTED = [
                                                   None, 0, 0, 0, 4, None, 0, None)),
     ("scan D = 129", "vc_mamba_scan_fwd", (1, 4, 129, 9, 1, None, None, None, None, None, None, None, None, None, None)),
     ("scan R = 65", "vc_mamba_scan_fwd", (1, 4, 72, 65, 1, None, None, None, None, None, None, None, None, None, None)),
+    # the spatial half (conv_gemm / conv_tap / conv / attention / rowchain / tokenlearner)
+    ("conv3x3 pad = 2", "vc_conv3x3_fwd", (1, 5, 5, 4, 4, 2, None, 4, None, None, None, None, None, None, 1, None, 4,
+                                           None, 0, None)),
+    ("conv3x3 ldy < O", "vc_conv3x3_fwd", (1, 5, 5, 4, 4, 0, None, 4, None, None, None, None, None, None, 1, None, 3,
+                                           None, 0, None)),
+    ("tap dgrad lddx < C", "vc_conv3x3_tap_dgrad", (1, 5, 5, 4, 4, 0, None, 4, None, 0.0, None, 3, None, 0, None)),
+    ("maxpool ldx < C", "vc_maxpool2_fwd", (1, 4, 4, 8, None, 7, None, None, None)),
+    ("nonlocal P = 17", "vc_nonlocal_attn_fwd", (1, 9, 17, 8, None, None, None, None, None)),
+    ("nonlocal P = 5 at Ci = 6 (no wave-per-row kernel for 5 keys)", "vc_nonlocal_attn_fwd",
+     (1, 9, 5, 6, None, None, None, None, None)),
+    ("nonlocal P = 5 with theta off 16 B", "vc_nonlocal_attn_fwd", (1, 9, 5, 8, 4, None, None, None, None)),
+    ("nonlocal backward P = 5 at Ci = 6", "vc_nonlocal_attn_bwd", (1, 9, 5, 6, None, None, None, None, None, None, None)),
+    ("nonlocal pool (Hs / 2)^2 != P", "vc_nonlocal_attn_pool_fwd", (1, 36, 4, 8, 6, None, None, 16, None, None, None,
+                                                                   None, None)),
+    ("nonlocal pool ldpg < 2 Ci", "vc_nonlocal_attn_pool_fwd", (1, 16, 4, 8, 4, None, None, 15, None, None, None, None,
+                                                                None)),
+    ("rowchain front E = 260", "vc_rowchain_front", (16, 144, 260, 144, None, None, None, 9, None, None, None, 1e-6, None,
+                                                     None, None, None, None, None)),
+    ("rowchain front K0 = 6", "vc_rowchain_front", (16, 6, 144, 144, None, None, None, 9, None, None, None, 1e-6, None,
+                                                    None, None, None, None, None)),
+    ("rowchain back_bwd dcd at address 4", "vc_rowchain_back_bwd", (16, 144, 144, 72, 4, None, None, None, None, None,
+                                                                    None, None, None, None, None, None, None, None)),
+    ("rowchain back_bwd Cout = 6", "vc_rowchain_back_bwd", (16, 6, 144, 72, None, None, None, None, None, None, None,
+                                                            None, None, None, None, None, None, None)),
+    ("rowchain front_bwd K0 = 6", "vc_rowchain_front_bwd", (16, 6, 144, 3, None, None, None, None, None, None, None, None,
+                                                            None, None, None, 0.0, None, None)),
+    ("rowchain front_bwd E = 6", "vc_rowchain_front_bwd", (16, 144, 6, 3, None, None, None, None, None, None, None, None,
+                                                           None, None, None, 0.0, None, None)),
+    ("tl_bwd C = 513", "vc_tl_bwd", (1, 2, 49, 513, 25, None, 513, None, None, None, None, None, None, None, None, None,
+                                     513, None, None)),
+    # (401 pixels with 324 tokens are accepted: the token and pixel chunks shrink until their LDS plans fit)
+    ("tl_check 30 x 30 pixels: no token chunk fits the LDS", "vc_tl_check", (900, 256, 324)),
+    ("tl_check C = 513", "vc_tl_check", (400, 513, 324)),
 ]
 
 

@@ -1,7 +1,9 @@
 """hsiMamba row chains (vc_rowchain_front / vc_rowchain_back, rowchain.hip) against the separate launches
 they replace (vc_gemm + vc_layernorm_fwd + vc_gemm; vc_mamba_combine_fwd + vc_gemm + vc_layernorm_fwd +
-vc_gemm) and a float64 evaluation: every output the backward reads, at both blocks' shapes, with a row
-count that leaves a partial 32-row block."""
+vc_gemm) and a float64 evaluation: every output the backward reads, at both blocks' shapes.  The row counts
+243, 245 and 3136 take the 16-row kernels (243 and 245 with a partial last block); 5184 = 162 x 32 takes the
+32-row kernels with whole blocks only.  A partial last 32-row block, widths that are no multiple of 16 and
+guarded outputs are in tests/test_rowchain_layouts_gpu.py."""
 import math
 
 import pytest

@@ -50,6 +50,18 @@ def _input(B, HW, C, seed, regime):
     return prof[None, :] * (1.0 + 1e-4 * torch.rand(B * HW, C, generator=g))
 
 
+def _buffers(x, par, S, regime, train):
+    """running (mean, var) [S, 2] of the tokens' BN(1)"""
+    buf = torch.stack([torch.rand(S) + 0.5, torch.rand(S) * 0.1 + 1e-3], 1)
+    if regime == "illcond" and not train:
+        # running statistics that match the ill-conditioned batch (eval normalises with them)
+        xm = x.max(1).values.double()
+        xa = x.double().mean(1)
+        f = par[:, 0:1].double() * xm[None] + par[:, 1:2].double() * xa[None] + par[:, 2:3].double()
+        buf = torch.stack([f.mean(1), f.var(1) * 4.0], 1).float()
+    return buf
+
+
 def _run_hip(L, train, x, B, HW, C, S, par, buf, dZ):
     M = B * HW
     P = lambda t: t.data_ptr()  # noqa: E731
@@ -120,13 +132,7 @@ def _close(got, ref, rtol):
 def test_tokenlearner_vs_float64(L, B, HW, C, S, regime, train):
     x = _input(B, HW, C, seed=B * 131 + C, regime=regime)
     par = _params(S, seed=S)
-    buf = torch.stack([torch.rand(S) + 0.5, torch.rand(S) * 0.1 + 1e-3], 1)
-    if regime == "illcond" and not train:
-        # running statistics that match the ill-conditioned batch (eval normalises with them)
-        xm = x.max(1).values.double()
-        xa = x.double().mean(1)
-        f = par[:, 0:1].double() * xm[None] + par[:, 1:2].double() * xa[None] + par[:, 2:3].double()
-        buf = torch.stack([f.mean(1), f.var(1) * 4.0], 1).float()
+    buf = _buffers(x, par, S, regime, train)
     g = torch.Generator().manual_seed(7)
     dZ = torch.rand(B * S * C, generator=g) * 2 - 1
     hip = _run_hip(L, train, x, B, HW, C, S, par, buf, dZ)
