@@ -675,4 +675,65 @@ VC_API int vc_xfusion_loss_fwd_bwd(int B, int ncls, const float* o1, const float
                                    const long long* target, const float* weight, float* loss, float* do1, float* do2,
                                    float* do3, hipStream_t stream);
 
+/* ---------------------------------------------------------------- per-pixel models (comparison models)
+ * model/compare_method/EndNet.py, spectralformer.py and losses.py:21-35.  All fp32, no atomics, fixed summation order.
+ *
+ * vc_fc_fused_fwd: one fully-connected layer in ONE launch, y = act(norm(x W^T + b)) for rows x [B, K] (row stride
+ *   ldx >= K, any alignment), W [N, K] dense, y [B, N] with row stride ldy >= N (two layers may write the two halves of
+ *   one wider buffer: a concat for free).  1 <= K <= VC_FC_KMAX.  mode:
+ *     VC_FC_PLAIN    y = z = x W^T + b
+ *     VC_FC_SIGMOID  y = 1 / (1 + exp(-z))
+ *     VC_FC_BN_RELU  y = relu(xhat gamma + beta), xhat = (z - mean) * rstd, nn.BatchNorm1d's conventions:
+ *       train = 1: mean and the biased variance over the B rows (two passes, the second over z - mean), rstd =
+ *         1 / sqrt(var + eps); run_mean = (1 - momentum) run_mean + momentum mean, run_var likewise with the unbiased
+ *         var B / (B - 1).  A workgroup owns 8 columns and every row, which it keeps in LDS: 2 <= B <=
+ *         VC_FC_TRAIN_BMAX, anything else is refused (return 1), never computed differently.
+ *       train = 0: mean = run_mean, rstd = 1 / sqrt(run_var + eps); rows are independent, any B.
+ *       xhat [B, N] dense (required in training, nullable in eval) and save_mean / save_rstd [N] (likewise) are what
+ *       the backward reads.
+ * vc_fc_fused_bwd: the same columns' backward in one launch, B <= VC_FC_TRAIN_BMAX, from dy [B, N] (row stride lddy):
+ *     g = dy                         (VC_FC_PLAIN)
+ *     g = dy y (1 - y)               (VC_FC_SIGMOID, y the forward's output, row stride ldy)
+ *     g = dy [y > 0]                 (VC_FC_BN_RELU); dbeta = sum_b g, dgamma = sum_b g xhat, and
+ *       dz = gamma rstd (g - dbeta / B - xhat dgamma / B) in training, dz = gamma rstd g in eval;
+ *   dz = g in the other modes.  dW[n, :] = sum_b dz[b, n] x[b, :], db[n] = sum_b dz[b, n] (overwritten); dz (nullable,
+ *   row stride lddz) is written for the caller's data-gradient GEMM dz W.
+ * vc_endnet_loss_fwd_bwd: EndNet_Loss for out [B, ncls], de1 / x1 [B, C1], de2 / x2 [B, C2] (dense):
+ *     loss = CE_weight(out, target) + mean((de1 - x1)^2) + mean((de2 - x2)^2)    (means over B C1 and B C2 elements)
+ *   and, for d(loss) = 1, dout = dCE, dde1 = 2 (de1 - x1) / (B C1), dde2 = 2 (de2 - x2) / (B C2), in ONE launch.
+ *   target int64 (-100 is ignored), weight may be null.  The cross-entropy half is vc_ce_fwd_bwd's code: with
+ *   de = x loss and dout are its bits.
+ * vc_sf_embed_fwd: SpectralFormer's token rows X [B, T, D], T = C1 + C2 + 1, from x1 [B, C1] and x2 [B, C2] (C1 >= 1;
+ *   C2 = 0 with x2 null is a single modality):
+ *     X[b, 0, :] = cls + pos[0];  X[b, 1 + n, :] = x[b, n] w + bias + pos[1 + n],  x = cat(x1, x2) along the bands
+ *   (Linear(1, D): w, bias [D]); pos [T, D].  With p > 0 the embedding dropout is applied to X with vc_dropout_fwd's
+ *   hash over the element index (the same seed gives the same keep mask) and the mask [B T D] bytes is written.
+ * vc_sf_embed_bwd: from dX [B, T, D] (with p > 0 first masked and scaled by 1 / (1 - p)):
+ *     dpos[t, d] = sum_b dX[b, t, d], dcls[d] = dpos[0, d], dw[d] = sum_{b, n} x[b, n] dX[b, 1 + n, d],
+ *     db[d] = sum_{b, n} dX[b, 1 + n, d]   (overwritten; per-(t, d) partials in ws >= T D floats, then a finishing
+ *   pass over t: two launches, fixed order). */
+#define VC_FC_PLAIN 0
+#define VC_FC_BN_RELU 1
+#define VC_FC_SIGMOID 2
+#define VC_FC_TRAIN_BMAX 1024
+#define VC_FC_KMAX 512
+VC_API int vc_fc_fused_fwd(int mode, int train, int B, int K, int N, const float* x, long ldx, const float* W,
+                           const float* bias, const float* gamma, const float* beta, float* run_mean, float* run_var,
+                           float eps, float momentum, float* y, long ldy, float* xhat, float* save_mean,
+                           float* save_rstd, hipStream_t stream);
+VC_API int vc_fc_fused_bwd(int mode, int train, int B, int K, int N, const float* dy, long lddy, const float* y,
+                           long ldy, const float* xhat, const float* x, long ldx, const float* gamma,
+                           const float* rstd, float* dz, long lddz, float* dW, float* db, float* dgamma, float* dbeta,
+                           hipStream_t stream);
+VC_API int vc_endnet_loss_fwd_bwd(int B, int ncls, int C1, int C2, const float* out, const long long* target,
+                                  const float* weight, const float* de1, const float* x1, const float* de2,
+                                  const float* x2, float* loss, float* dout, float* dde1, float* dde2,
+                                  hipStream_t stream);
+VC_API int vc_sf_embed_fwd(int B, int C1, int C2, int D, const float* x1, const float* x2, const float* w,
+                           const float* bias, const float* cls, const float* pos, float p, unsigned long long seed,
+                           float* X, unsigned char* mask, hipStream_t stream);
+VC_API int vc_sf_embed_bwd(int B, int C1, int C2, int D, const float* x1, const float* x2, const float* dX,
+                           const unsigned char* mask, float p, float* dw, float* db, float* dpos, float* dcls, float* ws,
+                           long ws_floats, hipStream_t stream);
+
 #endif /* VITCNN_H */

@@ -1,5 +1,5 @@
-"""Criteria on the MI355X: weighted cross-entropy (nn.CrossEntropyLoss(weight) of model_utils.py:311) and
-Cross_fusion_CNN's three-output loss (losses.py:7-19)."""
+"""Criteria on the MI355X: weighted cross-entropy (nn.CrossEntropyLoss(weight) of model_utils.py:311),
+Cross_fusion_CNN's three-output loss (losses.py:7-19) and EndNet's classification + reconstruction loss (losses.py:21-35)."""
 from __future__ import annotations
 
 import torch
@@ -119,3 +119,62 @@ class Cross_fusion_CNN_Loss(nn.Module):
                 w = w.to(o1.device)
         o1, o2, o3 = (o.to(torch.float32).contiguous() for o in (o1, o2, o3))
         return _CrossFusionLossFn.apply(o1, o2, o3, target.to(device=o1.device, dtype=torch.int64).contiguous(), w)
+
+
+class _EndNetLossFn(torch.autograd.Function):
+    """loss and the three gradients in one launch (vc_endnet_loss_fwd_bwd); the gradients wait side by side in one
+    buffer for the backward, which scales them by the incoming d(loss)"""
+
+    @staticmethod
+    def forward(ctx, out, de1, de2, x1, x2, target, weight):
+        B, ncls = out.shape
+        C1, C2 = de1.shape[1], de2.shape[1]
+        loss = torch.empty((), dtype=torch.float32, device=out.device)
+        grads = torch.empty(B * (ncls + C1 + C2), dtype=torch.float32, device=out.device)
+        s = torch.cuda.current_stream(out.device).cuda_stream
+        g0 = grads.data_ptr()
+        lib().vc_endnet_loss_fwd_bwd(B, ncls, C1, C2, out.data_ptr(), target.data_ptr(),
+                                     weight.data_ptr() if weight is not None else None, de1.data_ptr(), x1.data_ptr(),
+                                     de2.data_ptr(), x2.data_ptr(), loss.data_ptr(), g0, g0 + 4 * B * ncls,
+                                     g0 + 4 * B * (ncls + C1), s)
+        ctx.save_for_backward(grads)
+        ctx.dims = (B, ncls, C1, C2)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        (grads,) = ctx.saved_tensors
+        B, ncls, C1, C2 = ctx.dims
+        g = grads * gout.detach().to(torch.float32)
+        a, b = B * ncls, B * (ncls + C1)
+        return g[:a].view(B, ncls), g[a:b].view(B, C1), g[b:].view(B, C2), None, None, None, None
+
+
+class EndNet_Loss(nn.Module):
+    """Drop-in for the reference's EndNet_Loss(weight) (losses.py:21-35): for output = (out, de_x1, de_x2, ori_x1,
+    ori_x2), weighted mean CE(out, target) + mean((de_x1 - ori_x1)^2) + mean((de_x2 - ori_x2)^2)."""
+
+    def __init__(self, weight=None):
+        super().__init__()
+        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+
+    def forward(self, output, target: torch.Tensor) -> torch.Tensor:
+        out, de1, de2, x1, x2 = output
+        if out.device.type != "cuda":
+            raise RuntimeError("EndNet MI355X path: loss inputs must be on a ROCm (cuda) device")
+        B = out.shape[0]
+        x1, x2 = x1.reshape(B, -1), x2.reshape(B, -1)
+        if out.dim() != 2 or de1.shape != x1.shape or de2.shape != x2.shape or de1.dim() != 2 or target.dim() != 1 or \
+                target.shape[0] != B:
+            raise RuntimeError(f"expected out [B, C], two reconstructions shaped as their inputs and target [B], got "
+                               f"{list(out.shape)}, {list(de1.shape)} / {list(x1.shape)}, {list(de2.shape)} / "
+                               f"{list(x2.shape)}, {list(target.shape)}")
+        w = self.weight
+        if w is not None:
+            if w.numel() != out.shape[1]:
+                raise RuntimeError("weight tensor should be defined either for all classes or no classes")
+            if w.device != out.device:
+                w = w.to(out.device)
+        out, de1, de2 = (o.to(torch.float32).contiguous() for o in (out, de1, de2))
+        x1, x2 = (x.detach().to(torch.float32).contiguous() for x in (x1, x2))
+        return _EndNetLossFn.apply(out, de1, de2, x1, x2, target.to(device=out.device, dtype=torch.int64).contiguous(), w)

@@ -13,7 +13,8 @@ replaces, so `main.py`-style drivers switch by changing one import:
 Registered: "Multimodality_Mamba" (the README's "ViT-CNN (ours)"), "S2EFT" (config 5, :400-423),
 "FusAtNet" (config 5, :109-118), "MFT" (:364-376) and the four MDL-RS baselines "Early_fusion_CNN",
 "Middle_fusion_CNN", "Late_fusion_CNN" and "Cross_fusion_CNN" (:69-108; the last trains with
-`Cross_fusion_CNN_Loss` over its three outputs, and `val` / `test` read the first).
+`Cross_fusion_CNN_Loss` over its three outputs, and `val` / `test` read the first), and the per-pixel models
+"EndNet" (:119-128, `EndNet_Loss` over its five outputs) and "SpectralFormer" (:377-399), both with patch_size 1.
 The reference's other branches import modules absent from the reference tree (SURVEY.md section 2a
 row 22) and are out of scope for this path.
 
@@ -44,7 +45,7 @@ from .optim import AdamW
 from .window import SlidingWindowInference
 
 MDLRS = ("Early_fusion_CNN", "Middle_fusion_CNN", "Late_fusion_CNN", "Cross_fusion_CNN")
-REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT") + MDLRS
+REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT") + MDLRS + ("EndNet", "SpectralFormer")
 
 
 def camel_to_snake(name: str) -> str:
@@ -77,6 +78,10 @@ def get_model(name, **kwargs):
         return _get_mft(n_bands, n_bands2, n_classes, device, kwargs)
     if name in MDLRS:
         return _get_mdlrs(name, n_bands, n_bands2, n_classes, device, kwargs)
+    if name == "EndNet":
+        return _get_endnet(n_bands, n_bands2, n_classes, device, kwargs)
+    if name == "SpectralFormer":
+        return _get_spectralformer(n_bands, n_bands2, n_classes, device, kwargs)
     kwargs.setdefault("patch_size", 9)
     patch_size = kwargs["patch_size"]
     center_pixel = True
@@ -186,6 +191,47 @@ def _get_mdlrs(name, n_bands, n_bands2, n_classes, device, kwargs):
     kwargs.setdefault("epoch", 150)
     kwargs.setdefault("batch_size", 64)
     kwargs.setdefault("applyPCA", False)
+    kwargs.setdefault("supervision", "full")
+    kwargs["center_pixel"] = True
+    return model, optimizer, criterion, kwargs
+
+
+def _get_endnet(n_bands, n_bands2, n_classes, device, kwargs):
+    """EndNet branch of model_utils.py:119-128: EndNet(n_bands, n_bands2, n_classes), patch 1 (a pixel's two spectra),
+    Adam(lr 1e-3) -- the fused AdamW kernel with weight_decay 0, as FusAtNet --, EndNet_Loss(weight), epoch 150, batch 64,
+    applyPCA False (it does not change n_bands here, as in the reference)."""
+    from .endnet import EndNet
+    from .losses import EndNet_Loss
+    kwargs.setdefault("patch_size", 1)
+    model = EndNet(n_bands, n_bands2, n_classes).to(device)
+    lr = kwargs.setdefault("lr", 0.001)
+    optimizer = AdamW(model.parameters(), lr=lr, weight_decay=0.0)
+    criterion = EndNet_Loss(weight=kwargs["weights"])
+    kwargs.setdefault("epoch", 150)
+    kwargs.setdefault("batch_size", 64)
+    kwargs.setdefault("applyPCA", False)
+    kwargs.setdefault("supervision", "full")
+    kwargs["center_pixel"] = True
+    return model, optimizer, criterion, kwargs
+
+
+def _get_spectralformer(n_bands, n_bands2, n_classes, device, kwargs):
+    """SpectralFormer branch of model_utils.py:377-399: SpectralFormer(image_size=patch_size, near_band 1, num_patches =
+    n_bands + n_bands2 (n_bands 30 under applyPCA), dim 64, depth 5, heads 4, mlp_dim 8, dropout 0.1, emb_dropout 0.1,
+    mode 'ViT'), patch 1, Adam(lr 5e-4) as the fused AdamW with weight_decay 0, weighted CE, epoch 300, batch 64."""
+    from .spectralformer import SpectralFormer
+    kwargs.setdefault("patch_size", 1)
+    kwargs.setdefault("applyPCA", False)
+    if kwargs["applyPCA"]:
+        n_bands = 30
+    model = SpectralFormer(image_size=kwargs["patch_size"], near_band=1, num_patches=n_bands + n_bands2,
+                           num_classes=n_classes, dim=64, depth=5, heads=4, mlp_dim=8, dropout=0.1, emb_dropout=0.1,
+                           mode="ViT").to(device)
+    lr = kwargs.setdefault("lr", 0.0005)
+    optimizer = AdamW(model.parameters(), lr=lr, weight_decay=0.0)
+    criterion = CrossEntropyLoss(weight=kwargs["weights"])
+    kwargs.setdefault("epoch", 300)
+    kwargs.setdefault("batch_size", 64)
     kwargs.setdefault("supervision", "full")
     kwargs["center_pixel"] = True
     return model, optimizer, criterion, kwargs

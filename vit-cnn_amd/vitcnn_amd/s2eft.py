@@ -203,7 +203,12 @@ class _Program:
         return Y, mu, rs
 
     def forward(self):
-        m, L, B, T, N, C, D, Hh = self.m, self.L, self.B, self.T, self.m.N, self.m.C, self.m.D, self.m.heads
+        return self.layers(self.embed())
+
+    def embed(self):
+        """the token rows X [B, T, D] in front of the first layer (gate, cls row, patch embedding, position, dropout);
+        a model with another embedding (spectralformer.py) overrides this and `embed_bwd`"""
+        L, B, T, N, C, D = self.L, self.B, self.T, self.m.N, self.m.C, self.m.D
         R = B * T
         P = self.P
         xg, mask = self.new(B, N, C), self.new(B, N)
@@ -218,6 +223,13 @@ class _Program:
         if self.pe > 0:
             self.drop("emb", X, None, X, R * D, self.pe)
         self.xg = xg
+        return X
+
+    def layers(self, X):
+        """the pre-norm encoder layers and the head on the cls row: X [B, T, D] -> logits"""
+        m, L, B, T, D, Hh = self.m, self.L, self.B, self.T, self.m.D, self.m.heads
+        R = B * T
+        P = self.P
         self.saved = []
         xin = []
         for li in range(m.depth):
@@ -293,9 +305,7 @@ class _Program:
         writes a buffer the parameter gradients read (the LayerNorm backward writes the residual sum to a new
         buffer: vc_layernorm_bwd_dx with res), and every buffer they read stays referenced until the join.
         Per-launch arithmetic and per-stream order do not depend on the mode: the same bits."""
-        m, L, B, T, N, C, D, Hh = self.m, self.L, self.B, self.T, self.m.N, self.m.C, self.m.D, self.m.heads
-        R = B * T
-        P = self.P
+        m, L = self.m, self.L
         main = torch.cuda.current_stream(self.dev)
         side_stream = self._side_stream() if _SIDE_STREAM in (1, 2) else main
         scr2 = self.new(self.SCRATCH) if side_stream is not main else self.scr
@@ -335,6 +345,22 @@ class _Program:
         L.vc_fill(m._n_params, grad.data_ptr(), 0.0, self.s)
         gb = grad.data_ptr()
         G = {n: gb + F32 * o for n, o in m._poff.items()}
+        dX = self.layers_bwd(dlogits, G, sd, side, flush)
+        self.embed_bwd(dX, G, sd, side)
+        flush()
+        # join: the gradient is complete when the side stream is; its buffers may go back to the allocator after it
+        if side_stream is not main:
+            ev = torch.cuda.Event()
+            ev.record(side_stream)
+            main.wait_event(ev)
+        keep.clear()
+        return grad
+
+    def layers_bwd(self, dlogits, G, sd, side, flush):
+        """head and encoder layers: dlogits -> dX [B, T, D], the gradient of `embed`'s result"""
+        m, L, B, T, D, Hh = self.m, self.L, self.B, self.T, self.m.D, self.m.heads
+        R = B * T
+        P = self.P
         scr, ns = self.scr.data_ptr(), self.SCRATCH
         part_n = 1024 * 2 * D   # LayerNorm parameter partials (>= the kernel's partial rows: vc_layernorm_bwd's split)
 
@@ -431,7 +457,13 @@ class _Program:
             elif li in dlast:  # this layer's input is also last_output[li] of layer li + 2
                 L.vc_add2_2d(R, D, dX.data_ptr(), D, dlast[li].data_ptr(), D, dX.data_ptr(), D, 0.0, self.s)
             flush()   # _SIDE_STREAM 2: the layer's parameter gradients, one fork
-        # embedding: X0 = dropout(cat(cls, xg W^T + b) + pos)
+        return dX
+
+    def embed_bwd(self, dX, G, sd, side):
+        """embedding: X0 = dropout(cat(cls, xg W^T + b) + pos); its parameter gradients through `side`"""
+        L, B, T, N, C, D = self.L, self.B, self.T, self.m.N, self.m.C, self.m.D
+        R = B * T
+        ns = self.SCRATCH
         if self.pe > 0:
             L.vc_dropout_bwd(R * D, dX.data_ptr(), self.masks["emb"].data_ptr(), self.pe, dX.data_ptr(), self.s)
         dE = self.new(B * N, D)
@@ -441,14 +473,6 @@ class _Program:
              partial(L.vc_colsum, B, D, dX.data_ptr(), T * D, G["cls_token"], 0.0, sd[1], ns, sd[0]),
              partial(self.gemm, 1, 0, D, C, B * N, dE.data_ptr(), D, 0, self.xg.data_ptr(), C, 0, 0.0,
                      G["patch_to_embedding.weight"], C, 0, bias_grad=G["patch_to_embedding.bias"], side=sd))
-        flush()
-        # join: the gradient is complete when the side stream is; its buffers may go back to the allocator after it
-        if side_stream is not main:
-            ev = torch.cuda.Event()
-            ev.record(side_stream)
-            main.wait_event(ev)
-        keep.clear()
-        return grad
 
     def _group_buf(self):
         """host memory of the backward's grouped-GEMM state (vc_gemm_group_*: the library keeps none)"""
