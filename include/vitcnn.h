@@ -736,4 +736,65 @@ VC_API int vc_sf_embed_bwd(int B, int C1, int C2, int D, const float* x1, const 
                            const unsigned char* mask, float p, float* dw, float* db, float* dpos, float* dcls, float* ws,
                            long ws_floats, hipStream_t stream);
 
+/* ---------------------------------------------------------------- HCTnet (comparison model)
+ * model/compare_method/HCTnet.py.  All fp32 with fp32 accumulation, feature width 64, no atomics: every weight gradient
+ * is a per-sample partial row in ws summed in a fixed order, so a second call gives the same bits.  Dropout uses
+ * vc_dropout_fwd's hash over the element index of the call's whole mask buffer (keep = hash(seed, i) / 2^24 >= p, kept
+ * values scaled by 1 / (1 - p)); every keep decision is written out as a byte.  With every p of a call 0 the mask may be
+ * null; where it is given, p = 0 sites write 1.
+ *
+ * vc_hct_tokpool_fwd / _bwd: the tokeniser (HCTnet.py:326-353) for X [B*HW, 64] rows (ldx), 1 <= L <= 8 tokens,
+ *   1 <= HW <= 784, into a dense token buffer T [B, L+1, 64]:
+ *     A[b,l,:] = softmax_i(sum_j wA[l][j] X[b,i,j]),  U[b,l,j] = sum_i A[b,l,i] X[b,i,j],
+ *     T[b,0,:] = drop(cls + pos[0]),  T[b,1+l,k] = drop(sum_j U[b,l,j] wV[j][k] + pos[1+l][k])
+ *   ((A X) wV, a reassociation of A (X wV)); A [B,L,HW] and U [B,L,64] are saved, mask [B, L+1, 64] bytes.
+ *   bwd from dT [B, L+1, 64] (first masked and scaled): dX (lddx, overwritten) and one partial row per sample,
+ *   [L*64 dwA | 4096 dwV | (L+1)*64 dpos], at rows row0 .. row0 + B - 1 of ws (>= (row0 + B) * (L*64 + 4096 + (L+1)*64)
+ *   floats).  With dwA / dwV / dpos / dcls given (all or none) rows 0 .. row0 + B - 1 are then summed into them
+ *   (overwritten; dcls = dpos[0]): the model's two sources share the parameters, so the HSI call passes row0 = 0 and
+ *   no outputs, the LiDAR call row0 = B and the outputs, and both sources' partials are reduced together.
+ * vc_hct_encoder_fwd / _bwd: one pre-norm Transformer layer (HCTnet.py:205-219: Attention :56-94, MLP_Block :42-54)
+ *   of both branches' sequences X [2][B, T, 64] (branch stride strideX floats), 2 <= T <= 9, in ONE launch; a block
+ *   owns one sample of one branch.  W0 / W1: the branch's VC_HCT_ENC_FLOATS packed parameters in module order
+ *   [ln1.w 64 | ln1.b 64 | to_qkv.w 192x64 | to_qkv.b 192 | nn1.w 64x64 | nn1.b 64 | ln2.w 64 | ln2.b 64 | fc1.w 8x64 |
+ *   fc1.b 8 | fc2.w 64x8 | fc2.b 64] (16-B aligned):
+ *     n = LN(x) (eps 1e-5); q | k | v = n Wqkv^T + b split into 8 heads of width 8; a = softmax_j(0.125 q_i . k_j)
+ *     (the scale is 64^-0.5, the model width); o = a v; x2 = x + drop_a(o Wnn1^T + b);
+ *     y = x2 + drop_o(drop_h(gelu(LN(x2) Wfc1^T + b)) Wfc2^T + b)      (erf GELU)
+ *   pa / ph / po: the three sites' p per branch; mask [2][B][T*64 | T*8 | T*64] bytes.
+ *   bwd from dY (strideDY): dX (strideDX, overwritten) and dW0 / dW1 in the packed layout (overwritten); the forward's
+ *   intermediates are recomputed from X with the forward's code and the saved masks.  ws >= 2 B VC_HCT_ENC_FLOATS.
+ * vc_hct_ctattn_fwd / _bwd: the cross-token step (CT_Transformer :152-171, CTAttention :96-131) of both directions in
+ *   ONE launch from the encoder output X [2][B, T, 64]: direction d's query is branch d's row 0, its context
+ *   c = [LN(x[d][b][0]); x[1-d][b][1..T-1]] (T rows, only row 0 normed).  W0 / W1: VC_HCT_CT_FLOATS packed parameters
+ *   [ln.w 64 | ln.b 64 | to_q.w 512x64 | to_kv.w 1024x64 | to_out.w 64x512 | to_out.b 64] (16-B aligned):
+ *     q = Wq c_0; per head h (8 heads of width 64): a[h] = softmax_j(0.125 q_h . (Wk_h c_j)), ad = drop_p(a),
+ *     o_h = sum_j ad[h][j] Wv_h c_j;  out[d][b] = x[d][b][0] + drop_o(Wo o + bo)
+ *   evaluated as r_h = Wk_h^T q_h, score = r_h . c_j and o_h = Wv_h (sum_j ad[h][j] c_j): each weight is read once per
+ *   sample.  out [2][B, 64]; mask [2][B][8*T | 64] bytes.  bwd from dout [2][B,64]: dX [2][B,T,64] (strideDX,
+ *   overwritten: row 0 of branch d and rows 1.. of branch 1-d by direction d) and dW0 / dW1 packed (overwritten).
+ *   ws >= 2 B VC_HCT_CT_FLOATS. */
+#define VC_HCT_ENC_FLOATS 17992
+#define VC_HCT_CT_FLOATS 131264
+VC_API int vc_hct_tokpool_fwd(int B, int HW, int L, const float* X, long ldx, const float* wA, const float* wV,
+                              const float* cls, const float* pos, float p, unsigned long long seed, float* A, float* U,
+                              float* T, unsigned char* mask, hipStream_t stream);
+VC_API int vc_hct_tokpool_bwd(int B, int HW, int L, const float* X, long ldx, const float* wA, const float* wV,
+                              const float* A, const float* U, const float* dT, const unsigned char* mask, float p,
+                              float* dX, long lddx, float* ws, long ws_floats, int row0, float* dwA, float* dwV,
+                              float* dpos, float* dcls, hipStream_t stream);
+VC_API int vc_hct_encoder_fwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pa0,
+                              float ph0, float po0, float pa1, float ph1, float po1, unsigned long long seed, float* Y,
+                              long strideY, unsigned char* mask, hipStream_t stream);
+VC_API int vc_hct_encoder_bwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pa0,
+                              float ph0, float po0, float pa1, float ph1, float po1, const unsigned char* mask,
+                              const float* dY, long strideDY, float* dX, long strideDX, float* dW0, float* dW1,
+                              float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_hct_ctattn_fwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pp0,
+                             float po0, float pp1, float po1, unsigned long long seed, float* out, unsigned char* mask,
+                             hipStream_t stream);
+VC_API int vc_hct_ctattn_bwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pp0,
+                             float po0, float pp1, float po1, const unsigned char* mask, const float* dout, float* dX,
+                             long strideDX, float* dW0, float* dW1, float* ws, long ws_floats, hipStream_t stream);
+
 #endif /* VITCNN_H */

@@ -11,7 +11,8 @@ from .mft import MFT  # noqa: F401
 from .mdlrs import Cross_fusion_CNN, Early_fusion_CNN, Late_fusion_CNN, Middle_fusion_CNN  # noqa: F401
 from .endnet import EndNet  # noqa: F401
 from .spectralformer import SpectralFormer  # noqa: F401
+from .hctnet import HCTnet  # noqa: F401
 
 __all__ = ["Multimodality_Mamba", "CrossEntropyLoss", "Cross_fusion_CNN_Loss", "AdamW", "Adam", "MFT", "Early_fusion_CNN",
-           "Middle_fusion_CNN", "Late_fusion_CNN", "Cross_fusion_CNN", "EndNet", "SpectralFormer", "EndNet_Loss",
-           "fused_train_step"]
+           "Middle_fusion_CNN", "Late_fusion_CNN", "Cross_fusion_CNN", "EndNet", "SpectralFormer", "HCTnet",
+           "EndNet_Loss", "fused_train_step"]

@@ -14,7 +14,8 @@ Registered: "Multimodality_Mamba" (the README's "ViT-CNN (ours)"), "S2EFT" (conf
 "FusAtNet" (config 5, :109-118), "MFT" (:364-376) and the four MDL-RS baselines "Early_fusion_CNN",
 "Middle_fusion_CNN", "Late_fusion_CNN" and "Cross_fusion_CNN" (:69-108; the last trains with
 `Cross_fusion_CNN_Loss` over its three outputs, and `val` / `test` read the first), and the per-pixel models
-"EndNet" (:119-128, `EndNet_Loss` over its five outputs) and "SpectralFormer" (:377-399), both with patch_size 1.
+"EndNet" (:119-128, `EndNet_Loss` over its five outputs) and "SpectralFormer" (:377-399), both with patch_size 1, and
+"HCTnet" (:351-363; the HSI cube reduced to 3 principal components, `PatchBatcher(applyPCA=True)`).
 The reference's other branches import modules absent from the reference tree (SURVEY.md section 2a
 row 22) and are out of scope for this path.
 
@@ -45,7 +46,7 @@ from .optim import AdamW
 from .window import SlidingWindowInference
 
 MDLRS = ("Early_fusion_CNN", "Middle_fusion_CNN", "Late_fusion_CNN", "Cross_fusion_CNN")
-REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT") + MDLRS + ("EndNet", "SpectralFormer")
+REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT") + MDLRS + ("EndNet", "SpectralFormer", "HCTnet")
 
 
 def camel_to_snake(name: str) -> str:
@@ -82,6 +83,8 @@ def get_model(name, **kwargs):
         return _get_endnet(n_bands, n_bands2, n_classes, device, kwargs)
     if name == "SpectralFormer":
         return _get_spectralformer(n_bands, n_bands2, n_classes, device, kwargs)
+    if name == "HCTnet":
+        return _get_hctnet(n_bands, n_classes, device, kwargs)
     kwargs.setdefault("patch_size", 9)
     patch_size = kwargs["patch_size"]
     center_pixel = True
@@ -231,6 +234,27 @@ def _get_spectralformer(n_bands, n_bands2, n_classes, device, kwargs):
     optimizer = AdamW(model.parameters(), lr=lr, weight_decay=0.0)
     criterion = CrossEntropyLoss(weight=kwargs["weights"])
     kwargs.setdefault("epoch", 300)
+    kwargs.setdefault("batch_size", 64)
+    kwargs.setdefault("supervision", "full")
+    kwargs["center_pixel"] = True
+    return model, optimizer, criterion, kwargs
+
+
+def _get_hctnet(n_bands, n_classes, device, kwargs):
+    """HCTnet branch of model_utils.py:351-363: HCTnet(num_classes, num_tokens 6, heads 8) -- no band count is passed:
+    the model takes the HSI cube reduced to 3 components, which `applyPCA` (default True here) makes of it in
+    `PatchBatcher(applyPCA=True)` and `test()` --, patch 11, Adam(lr 1e-4) as the fused AdamW with weight_decay 0,
+    weighted CE, epoch 100, batch 64.  n_bands = 30 under applyPCA is the reference's line and is unused."""
+    from .hctnet import HCTnet
+    kwargs.setdefault("patch_size", 11)
+    kwargs.setdefault("applyPCA", True)
+    if kwargs["applyPCA"]:
+        n_bands = 30   # noqa: F841 (as the reference writes it; the constructor takes no band count)
+    model = HCTnet(num_classes=n_classes, num_tokens=6, heads=8).to(device)
+    lr = kwargs.setdefault("lr", 0.0001)
+    optimizer = AdamW(model.parameters(), lr=lr, weight_decay=0.0)
+    criterion = CrossEntropyLoss(weight=kwargs["weights"])
+    kwargs.setdefault("epoch", 100)
     kwargs.setdefault("batch_size", 64)
     kwargs.setdefault("supervision", "full")
     kwargs["center_pixel"] = True

@@ -107,8 +107,12 @@ class PatchBatcher:
 
     def __init__(self, img1, img2, gt, patch_size: int, ignored_labels=(0,), batch_size: int = 64,
                  flip_augmentation: bool = False, device="cuda", seed: int = 0, rank: int = 0, world: int = 1,
-                 name: str = "synthetic", radiation_augmentation: bool = False, mixture_augmentation: bool = False):
+                 name: str = "synthetic", radiation_augmentation: bool = False, mixture_augmentation: bool = False,
+                 applyPCA: bool = False):
         self.device = torch.device(device)
+        if applyPCA:   # MultiModalX (datasets.py:507-508): the HSI cube reduced to 3 components before any patch is cut
+            from .model_utils import apply_pca
+            img1 = apply_pca(np.asarray(img1), 3)
         self.c1, self.c2 = _cube(img1, self.device), _cube(img2, self.device)
         self.P, self.bs, self.flip = int(patch_size), int(batch_size), bool(flip_augmentation)
         self.radiation, self.mixture = bool(radiation_augmentation), bool(mixture_augmentation)
