@@ -555,6 +555,17 @@ VC_API int vc_s2eft_skip_bias_grad(int B, int T, int D, const float* dY, float* 
 VC_API int vc_dropout_fwd(long n, const float* x, const float* add, float* y, unsigned char* mask, float p,
                           unsigned long long seed, hipStream_t stream);
 VC_API int vc_dropout_bwd(long n, const float* dy, const unsigned char* mask, float p, float* dx, hipStream_t stream);
+/* The step seed in device memory, so that a replayed hipGraph of a training step draws fresh
+ * keep masks.  state: 4 x unsigned long long {base, step, cur, 0} (8-byte aligned).  vc_seed_next is one launch of
+ * one thread: step += 1, cur = splitmix64(base + step * 0x9E3779B97F4A7C15) >> 2 (wrapping 64-bit arithmetic;
+ * cur < 2^62, the range of the host seeds); vitcnn_amd/seeds.py step_seed(base, step) restates it.
+ * Every seed-taking forward has a _ds twin that reads its seed there: seed_dev points at `cur`, and the effective
+ * seed is *seed_dev + site_offset (no wrap for site offsets < 2^62).  With *seed_dev == v a _ds call writes the
+ * outputs and mask bytes of its host-seed entry called with seed v + site_offset, bit for bit (one kernel body: the
+ * host-seed entry passes a null seed_dev).  The backward kernels read the saved mask bytes and have no twin. */
+VC_API int vc_seed_next(unsigned long long* state, hipStream_t stream);
+VC_API int vc_dropout_fwd_ds(long n, const float* x, const float* add, float* y, unsigned char* mask, float p,
+                             const unsigned long long* seed_dev, unsigned long long site_offset, hipStream_t stream);
 
 /* ---------------------------------------------------------------- FusAtNet forward (config 5)
  * model/compare_method/FusAtNet.py over channels-last [B,H,W,C] rows.
@@ -732,6 +743,11 @@ VC_API int vc_endnet_loss_fwd_bwd(int B, int ncls, int C1, int C2, const float* 
 VC_API int vc_sf_embed_fwd(int B, int C1, int C2, int D, const float* x1, const float* x2, const float* w,
                            const float* bias, const float* cls, const float* pos, float p, unsigned long long seed,
                            float* X, unsigned char* mask, hipStream_t stream);
+/* vc_sf_embed_fwd with the seed *seed_dev + site_offset read on the device (see vc_seed_next) */
+VC_API int vc_sf_embed_fwd_ds(int B, int C1, int C2, int D, const float* x1, const float* x2, const float* w,
+                              const float* bias, const float* cls, const float* pos, float p,
+                              const unsigned long long* seed_dev, unsigned long long site_offset, float* X,
+                              unsigned char* mask, hipStream_t stream);
 VC_API int vc_sf_embed_bwd(int B, int C1, int C2, int D, const float* x1, const float* x2, const float* dX,
                            const unsigned char* mask, float p, float* dw, float* db, float* dpos, float* dcls, float* ws,
                            long ws_floats, hipStream_t stream);
@@ -796,5 +812,18 @@ VC_API int vc_hct_ctattn_fwd(int B, int T, const float* X, long strideX, const f
 VC_API int vc_hct_ctattn_bwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pp0,
                              float po0, float pp1, float po1, const unsigned char* mask, const float* dout, float* dX,
                              long strideDX, float* dW0, float* dW1, float* ws, long ws_floats, hipStream_t stream);
+/* the three forwards with the seed *seed_dev + site_offset read on the device (see vc_seed_next); everything else as
+ * the host-seed entries above */
+VC_API int vc_hct_tokpool_fwd_ds(int B, int HW, int L, const float* X, long ldx, const float* wA, const float* wV,
+                                 const float* cls, const float* pos, float p, const unsigned long long* seed_dev,
+                                 unsigned long long site_offset, float* A, float* U, float* T, unsigned char* mask,
+                                 hipStream_t stream);
+VC_API int vc_hct_encoder_fwd_ds(int B, int T, const float* X, long strideX, const float* W0, const float* W1,
+                                 float pa0, float ph0, float po0, float pa1, float ph1, float po1,
+                                 const unsigned long long* seed_dev, unsigned long long site_offset, float* Y,
+                                 long strideY, unsigned char* mask, hipStream_t stream);
+VC_API int vc_hct_ctattn_fwd_ds(int B, int T, const float* X, long strideX, const float* W0, const float* W1,
+                                float pp0, float po0, float pp1, float po1, const unsigned long long* seed_dev,
+                                unsigned long long site_offset, float* out, unsigned char* mask, hipStream_t stream);
 
 #endif /* VITCNN_H */

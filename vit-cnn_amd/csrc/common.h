@@ -203,6 +203,13 @@ __device__ __forceinline__ bool block_last_arriver(unsigned int* cnt, unsigned n
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
+// A dropout site's seed: the host scalar of the launch, or (the _ds entries) the step seed in
+// device memory plus the site's offset, which arrives in the scalar's place.  One uniform load at kernel entry.
+__device__ __forceinline__ unsigned long long vc_site_seed(unsigned long long seed,
+                                                           const unsigned long long* __restrict__ seed_dev) {
+  return seed_dev ? *seed_dev + seed : seed;
+}
+
 // torch.nn.functional.softplus(beta=1, threshold=20)
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.0f ? x : log1pf(__expf(x)); }
 

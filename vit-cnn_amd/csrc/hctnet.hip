@@ -86,8 +86,10 @@ static __global__ __launch_bounds__(512) void hct_tokpool_fwd(int HW, int L, con
                                                               const float* __restrict__ wV,
                                                               const float* __restrict__ cls,
                                                               const float* __restrict__ pos, float p,
-                                                              unsigned long long seed, float* __restrict__ A,
-                                                              float* __restrict__ U, float* __restrict__ T,
+                                                              unsigned long long seed,
+                                                              const unsigned long long* __restrict__ seed_dev,
+                                                              float* __restrict__ A, float* __restrict__ U,
+                                                              float* __restrict__ T,
                                                               unsigned char* __restrict__ mask) {
   __shared__ float sA[HCT_LMAX][HCT_HW_MAX];
   __shared__ float sU[HCT_LMAX][HCT_F];
@@ -95,7 +97,7 @@ static __global__ __launch_bounds__(512) void hct_tokpool_fwd(int HW, int L, con
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* Xb = X + (long)b * HW * ldx;
   const long tb = (long)b * (L + 1) * HCT_F;
-  const HctDrop dr = hct_drop(mask, tb, p, seed, true);
+  const HctDrop dr = hct_drop(mask, tb, p, vc_site_seed(seed, seed_dev), true);
   if (tid < L * HCT_F) swA[tid >> 6][tid & 63] = wA[tid];
   __syncthreads();
   for (int i = tid; i < HW; i += 512) {
@@ -224,16 +226,31 @@ static inline bool hct_tok_ok(int B, int HW, int L, long ldx) {
          (long)B * HW * ldx < (1L << 31);
 }
 
-VC_API int vc_hct_tokpool_fwd(int B, int HW, int L, const float* X, long ldx, const float* wA, const float* wV,
-                              const float* cls, const float* pos, float p, unsigned long long seed, float* A, float* U,
-                              float* T, unsigned char* mask, hipStream_t stream) {
+static int hct_tokpool_fwd_launch(int B, int HW, int L, const float* X, long ldx, const float* wA, const float* wV,
+                                  const float* cls, const float* pos, float p, unsigned long long seed,
+                                  const unsigned long long* seed_dev, float* A, float* U, float* T,
+                                  unsigned char* mask, hipStream_t stream) {
   VC_REQUIRE(hct_tok_ok(B, HW, L, ldx));
   VC_REQUIRE(p >= 0.f && p < 1.f && (p == 0.f || mask));
   VC_REQUIRE(X && wA && wV && cls && pos && A && U && T);
-  hipLaunchKernelGGL(hct_tokpool_fwd, dim3(B), dim3(512), 0, stream, HW, L, X, ldx, wA, wV, cls, pos, p, seed, A, U, T,
-                     mask);
+  hipLaunchKernelGGL(hct_tokpool_fwd, dim3(B), dim3(512), 0, stream, HW, L, X, ldx, wA, wV, cls, pos, p, seed,
+                     seed_dev, A, U, T, mask);
   VC_CHECK_LAUNCH();
   return VC_OK;
+}
+
+VC_API int vc_hct_tokpool_fwd(int B, int HW, int L, const float* X, long ldx, const float* wA, const float* wV,
+                              const float* cls, const float* pos, float p, unsigned long long seed, float* A, float* U,
+                              float* T, unsigned char* mask, hipStream_t stream) {
+  return hct_tokpool_fwd_launch(B, HW, L, X, ldx, wA, wV, cls, pos, p, seed, nullptr, A, U, T, mask, stream);
+}
+
+VC_API int vc_hct_tokpool_fwd_ds(int B, int HW, int L, const float* X, long ldx, const float* wA, const float* wV,
+                                 const float* cls, const float* pos, float p, const unsigned long long* seed_dev,
+                                 unsigned long long site_offset, float* A, float* U, float* T, unsigned char* mask,
+                                 hipStream_t stream) {
+  VC_REQUIRE(seed_dev);
+  return hct_tokpool_fwd_launch(B, HW, L, X, ldx, wA, wV, cls, pos, p, site_offset, seed_dev, A, U, T, mask, stream);
 }
 
 VC_API int vc_hct_tokpool_bwd(int B, int HW, int L, const float* X, long ldx, const float* wA, const float* wV,
@@ -434,9 +451,12 @@ struct EncP {
 static __global__ __launch_bounds__(256) void hct_encoder_fwd(int B, int T, const float* __restrict__ X, long strideX,
                                                               const float* __restrict__ W0,
                                                               const float* __restrict__ W1, EncP p0, EncP p1,
-                                                              unsigned long long seed, float* __restrict__ Y,
-                                                              long strideY, unsigned char* __restrict__ mask) {
+                                                              unsigned long long seed,
+                                                              const unsigned long long* __restrict__ seed_dev,
+                                                              float* __restrict__ Y, long strideY,
+                                                              unsigned char* __restrict__ mask) {
   __shared__ EncFwd s;
+  seed = vc_site_seed(seed, seed_dev);
   const int b = blockIdx.x, br = blockIdx.y;
   const float* W = br ? W1 : W0;
   const EncP p = br ? p1 : p0;
@@ -602,19 +622,36 @@ static inline bool hct_seq_ok(int B, int T, long stride) {
          2L * B * T * E_MASK < (1L << 31);
 }
 
-VC_API int vc_hct_encoder_fwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pa0,
-                              float ph0, float po0, float pa1, float ph1, float po1, unsigned long long seed, float* Y,
-                              long strideY, unsigned char* mask, hipStream_t stream) {
+static int hct_encoder_fwd_launch(int B, int T, const float* X, long strideX, const float* W0, const float* W1,
+                                  float pa0, float ph0, float po0, float pa1, float ph1, float po1,
+                                  unsigned long long seed, const unsigned long long* seed_dev, float* Y, long strideY,
+                                  unsigned char* mask, hipStream_t stream) {
   VC_REQUIRE(hct_seq_ok(B, T, strideX) && strideY >= (long)B * T * HCT_F);
   VC_REQUIRE(hct_p_ok(pa0) && hct_p_ok(ph0) && hct_p_ok(po0) && hct_p_ok(pa1) && hct_p_ok(ph1) && hct_p_ok(po1));
   const bool any = pa0 > 0.f || ph0 > 0.f || po0 > 0.f || pa1 > 0.f || ph1 > 0.f || po1 > 0.f;
   VC_REQUIRE(X && W0 && W1 && Y && (mask || !any));
   VC_REQUIRE((((uintptr_t)W0 | (uintptr_t)W1) & 15) == 0);
   const EncP p0{pa0, ph0, po0}, p1{pa1, ph1, po1};
-  hipLaunchKernelGGL(hct_encoder_fwd, dim3(B, 2), dim3(256), 0, stream, B, T, X, strideX, W0, W1, p0, p1, seed, Y,
-                     strideY, mask);
+  hipLaunchKernelGGL(hct_encoder_fwd, dim3(B, 2), dim3(256), 0, stream, B, T, X, strideX, W0, W1, p0, p1, seed,
+                     seed_dev, Y, strideY, mask);
   VC_CHECK_LAUNCH();
   return VC_OK;
+}
+
+VC_API int vc_hct_encoder_fwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pa0,
+                              float ph0, float po0, float pa1, float ph1, float po1, unsigned long long seed, float* Y,
+                              long strideY, unsigned char* mask, hipStream_t stream) {
+  return hct_encoder_fwd_launch(B, T, X, strideX, W0, W1, pa0, ph0, po0, pa1, ph1, po1, seed, nullptr, Y, strideY, mask,
+                                stream);
+}
+
+VC_API int vc_hct_encoder_fwd_ds(int B, int T, const float* X, long strideX, const float* W0, const float* W1,
+                                 float pa0, float ph0, float po0, float pa1, float ph1, float po1,
+                                 const unsigned long long* seed_dev, unsigned long long site_offset, float* Y,
+                                 long strideY, unsigned char* mask, hipStream_t stream) {
+  VC_REQUIRE(seed_dev);
+  return hct_encoder_fwd_launch(B, T, X, strideX, W0, W1, pa0, ph0, po0, pa1, ph1, po1, site_offset, seed_dev, Y,
+                                strideY, mask, stream);
 }
 
 VC_API int vc_hct_encoder_bwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pa0,
@@ -759,8 +796,10 @@ struct CtP {
 static __global__ __launch_bounds__(256) void hct_ctattn_fwd(int B, int T, const float* __restrict__ X, long strideX,
                                                              const float* __restrict__ W0, const float* __restrict__ W1,
                                                              CtP p0, CtP p1, unsigned long long seed,
+                                                             const unsigned long long* __restrict__ seed_dev,
                                                              float* __restrict__ out, unsigned char* __restrict__ mask) {
   __shared__ CtFwd s;
+  seed = vc_site_seed(seed, seed_dev);
   const int b = blockIdx.x, d = blockIdx.y;
   const CtP p = d ? p1 : p0;
   const long mb = ((long)d * B + b) * (C_HEADS * T + 64);
@@ -864,19 +903,33 @@ static __global__ __launch_bounds__(256) void hct_ctattn_bwd(int B, int T, const
   for (int e = 64 + tid; e < T * 64; e += 256) dXc[e] = g.dc[e];
 }
 
-VC_API int vc_hct_ctattn_fwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pp0,
-                             float po0, float pp1, float po1, unsigned long long seed, float* out, unsigned char* mask,
-                             hipStream_t stream) {
+static int hct_ctattn_fwd_launch(int B, int T, const float* X, long strideX, const float* W0, const float* W1,
+                                 float pp0, float po0, float pp1, float po1, unsigned long long seed,
+                                 const unsigned long long* seed_dev, float* out, unsigned char* mask,
+                                 hipStream_t stream) {
   VC_REQUIRE(hct_seq_ok(B, T, strideX));
   VC_REQUIRE(hct_p_ok(pp0) && hct_p_ok(po0) && hct_p_ok(pp1) && hct_p_ok(po1));
   const bool any = pp0 > 0.f || po0 > 0.f || pp1 > 0.f || po1 > 0.f;
   VC_REQUIRE(X && W0 && W1 && out && (mask || !any));
   VC_REQUIRE((((uintptr_t)W0 | (uintptr_t)W1) & 15) == 0);
   const CtP p0{pp0, po0}, p1{pp1, po1};
-  hipLaunchKernelGGL(hct_ctattn_fwd, dim3(B, 2), dim3(256), 0, stream, B, T, X, strideX, W0, W1, p0, p1, seed, out,
-                     mask);
+  hipLaunchKernelGGL(hct_ctattn_fwd, dim3(B, 2), dim3(256), 0, stream, B, T, X, strideX, W0, W1, p0, p1, seed,
+                     seed_dev, out, mask);
   VC_CHECK_LAUNCH();
   return VC_OK;
+}
+
+VC_API int vc_hct_ctattn_fwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pp0,
+                             float po0, float pp1, float po1, unsigned long long seed, float* out, unsigned char* mask,
+                             hipStream_t stream) {
+  return hct_ctattn_fwd_launch(B, T, X, strideX, W0, W1, pp0, po0, pp1, po1, seed, nullptr, out, mask, stream);
+}
+
+VC_API int vc_hct_ctattn_fwd_ds(int B, int T, const float* X, long strideX, const float* W0, const float* W1,
+                                float pp0, float po0, float pp1, float po1, const unsigned long long* seed_dev,
+                                unsigned long long site_offset, float* out, unsigned char* mask, hipStream_t stream) {
+  VC_REQUIRE(seed_dev);
+  return hct_ctattn_fwd_launch(B, T, X, strideX, W0, W1, pp0, po0, pp1, po1, site_offset, seed_dev, out, mask, stream);
 }
 
 VC_API int vc_hct_ctattn_bwd(int B, int T, const float* X, long strideX, const float* W0, const float* W1, float pp0,

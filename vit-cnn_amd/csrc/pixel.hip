@@ -330,9 +330,11 @@ __device__ __forceinline__ uint32_t sf_mix32(uint64_t seed, uint32_t i) {
 __global__ void sf_embed_fwd(int total, FastDiv fD, FastDiv fT, int C1, int C2, const float* __restrict__ x1,
                              const float* __restrict__ x2, const float* __restrict__ w, const float* __restrict__ bias,
                              const float* __restrict__ cls, const float* __restrict__ pos, float p, float scale,
-                             unsigned long long seed, float* __restrict__ X, unsigned char* __restrict__ mask) {
+                             unsigned long long seed, const unsigned long long* __restrict__ seed_dev,
+                             float* __restrict__ X, unsigned char* __restrict__ mask) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
+  if (p > 0.f) seed = vc_site_seed(seed, seed_dev);
   int d, t;
   const int q = fdivmod(i, fD, d);
   const int b = fdivmod(q, fT, t);
@@ -445,17 +447,32 @@ VC_API int vc_endnet_loss_fwd_bwd(int B, int ncls, int C1, int C2, const float* 
   return VC_OK;
 }
 
-VC_API int vc_sf_embed_fwd(int B, int C1, int C2, int D, const float* x1, const float* x2, const float* w,
-                           const float* bias, const float* cls, const float* pos, float p, unsigned long long seed,
-                           float* X, unsigned char* mask, hipStream_t stream) {
+static int sf_embed_fwd_launch(int B, int C1, int C2, int D, const float* x1, const float* x2, const float* w,
+                               const float* bias, const float* cls, const float* pos, float p, unsigned long long seed,
+                               const unsigned long long* seed_dev, float* X, unsigned char* mask, hipStream_t stream) {
   VC_REQUIRE(B > 0 && C1 > 0 && C2 >= 0 && D > 0 && p >= 0.f && p < 1.f);
   const long total = (long)B * (C1 + C2 + 1) * D;
   VC_REQUIRE_I32(total);
   VC_REQUIRE(x1 && (x2 || C2 == 0) && w && bias && cls && pos && X && (p == 0.f || mask));
   hipLaunchKernelGGL(sf_embed_fwd, dim3(vc_cdiv(total, 256)), dim3(256), 0, stream, (int)total, make_fastdiv(D),
-                     make_fastdiv(C1 + C2 + 1), C1, C2, x1, x2, w, bias, cls, pos, p, 1.0f / (1.0f - p), seed, X, mask);
+                     make_fastdiv(C1 + C2 + 1), C1, C2, x1, x2, w, bias, cls, pos, p, 1.0f / (1.0f - p), seed, seed_dev,
+                     X, mask);
   VC_CHECK_LAUNCH();
   return VC_OK;
+}
+
+VC_API int vc_sf_embed_fwd(int B, int C1, int C2, int D, const float* x1, const float* x2, const float* w,
+                           const float* bias, const float* cls, const float* pos, float p, unsigned long long seed,
+                           float* X, unsigned char* mask, hipStream_t stream) {
+  return sf_embed_fwd_launch(B, C1, C2, D, x1, x2, w, bias, cls, pos, p, seed, nullptr, X, mask, stream);
+}
+
+VC_API int vc_sf_embed_fwd_ds(int B, int C1, int C2, int D, const float* x1, const float* x2, const float* w,
+                              const float* bias, const float* cls, const float* pos, float p,
+                              const unsigned long long* seed_dev, unsigned long long site_offset, float* X,
+                              unsigned char* mask, hipStream_t stream) {
+  VC_REQUIRE(seed_dev);
+  return sf_embed_fwd_launch(B, C1, C2, D, x1, x2, w, bias, cls, pos, p, site_offset, seed_dev, X, mask, stream);
 }
 
 VC_API int vc_sf_embed_bwd(int B, int C1, int C2, int D, const float* x1, const float* x2, const float* dX,

@@ -400,9 +400,11 @@ __device__ __forceinline__ uint32_t mix32(uint64_t seed, uint32_t i) {
 }
 
 __global__ void dropout_fwd(int n, const float* __restrict__ x, const float* __restrict__ add, float* __restrict__ y,
-                            unsigned char* __restrict__ mask, float p, float scale, unsigned long long seed) {
+                            unsigned char* __restrict__ mask, float p, float scale, unsigned long long seed,
+                            const unsigned long long* __restrict__ seed_dev) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  seed = vc_site_seed(seed, seed_dev);
   const float u = (float)(mix32(seed, (uint32_t)i) >> 8) * (1.0f / 16777216.0f);
   const bool keep = u >= p;
   const float v = keep ? x[i] * scale : 0.f;
@@ -419,13 +421,47 @@ __global__ void dropout_bwd(int n, const float* __restrict__ dy, const unsigned 
 
 }  // namespace
 
-VC_API int vc_dropout_fwd(long n, const float* x, const float* add, float* y, unsigned char* mask, float p,
-                          unsigned long long seed, hipStream_t stream) {
+static int dropout_fwd_launch(long n, const float* x, const float* add, float* y, unsigned char* mask, float p,
+                              unsigned long long seed, const unsigned long long* seed_dev, hipStream_t stream) {
   VC_REQUIRE(n >= 0 && p >= 0.f && p < 1.f);
   VC_REQUIRE_I32(n);
   if (n == 0) return VC_OK;
   hipLaunchKernelGGL(dropout_fwd, dim3(vc_cdiv(n, 256)), dim3(256), 0, stream, (int)n, x, add, y, mask, p,
-                     1.0f / (1.0f - p), seed);
+                     1.0f / (1.0f - p), seed, seed_dev);
+  VC_CHECK_LAUNCH();
+  return VC_OK;
+}
+
+VC_API int vc_dropout_fwd(long n, const float* x, const float* add, float* y, unsigned char* mask, float p,
+                          unsigned long long seed, hipStream_t stream) {
+  return dropout_fwd_launch(n, x, add, y, mask, p, seed, nullptr, stream);
+}
+
+VC_API int vc_dropout_fwd_ds(long n, const float* x, const float* add, float* y, unsigned char* mask, float p,
+                             const unsigned long long* seed_dev, unsigned long long site_offset, hipStream_t stream) {
+  VC_REQUIRE(seed_dev);
+  return dropout_fwd_launch(n, x, add, y, mask, p, site_offset, seed_dev, stream);
+}
+
+// ------------------------------------------------------------------ the step seed in device memory
+// state = {base, step, cur, 0}: step += 1, cur = splitmix64(base + step * golden) >> 2 (< 2^62, the range of the host
+// seeds).  One thread, plain stores; vitcnn_amd/seeds.py step_seed restates it.
+namespace {
+__global__ void seed_next(unsigned long long* __restrict__ state) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const unsigned long long step = state[1] + 1ull;
+  unsigned long long z = state[0] + step * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  state[1] = step;
+  state[2] = z >> 2;
+}
+}  // namespace
+
+VC_API int vc_seed_next(unsigned long long* state, hipStream_t stream) {
+  VC_REQUIRE(state && ((uintptr_t)state & 7) == 0);
+  hipLaunchKernelGGL(seed_next, dim3(1), dim3(1), 0, stream, state);
   VC_CHECK_LAUNCH();
   return VC_OK;
 }

@@ -30,6 +30,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from . import seeds
 from ._lib import lib
 from .flat import F32, FlatParams
 from .fusatnet import _counters   # one zeroed arrival-counter array per (device, stream)
@@ -288,7 +289,10 @@ class _Program:
         self.W = {k: base + F32 * o for k, o in m._packed.items()}
         self.masks = {}
         self.seed = 0
-        if self.train and any(p > 0 for p in self._drop_ps()):
+        drops = self.train and any(p > 0 for p in self._drop_ps())
+        # a device-resident step seed (seeds.attach): nothing is drawn on the host, the _ds entries read it there
+        self.dseed = seeds.state_for(m, self.dev) if drops else None
+        if drops and self.dseed is None:
             self.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             # data parallelism: every rank seeds torch alike, so mix the rank in -- the replicas must not apply
             # the same keep masks to their different shards
@@ -394,23 +398,29 @@ class _Program:
         AH, UH, AL, UL = self.new(B, Lt, H2 * H2), self.new(B, Lt, DIM), self.new(B, Lt, H1 * H1), self.new(B, Lt, DIM)
         mk_h = self.bytes(B, T, DIM) if tr else None
         mk_l = self.bytes(B, T, DIM) if tr else None
+        ds = self.dseed
         for k, (src, HW, A, U, mk) in enumerate(((z2, H2 * H2, AH, UH, mk_h), (zl, H1 * H1, AL, UL, mk_l))):
-            L.vc_hct_tokpool_fwd(B, HW, Lt, src.data_ptr(), DIM, P["token_wA"], P["token_wV"], P["cls_token"],
-                                 P["pos_embedding"], pe, self.site_seed(k), A.data_ptr(), U.data_ptr(),
-                                 X0[k].data_ptr(), mk.data_ptr() if mk is not None else None, s)
+            seed = (ds.cur_ptr, 1000003 * k) if ds is not None else (self.site_seed(k),)
+            (L.vc_hct_tokpool_fwd_ds if ds is not None else L.vc_hct_tokpool_fwd)(
+                B, HW, Lt, src.data_ptr(), DIM, P["token_wA"], P["token_wV"], P["cls_token"], P["pos_embedding"], pe,
+                *seed, A.data_ptr(), U.data_ptr(), X0[k].data_ptr(), mk.data_ptr() if mk is not None else None, s)
         # the two encoder layers (:200), one launch
         ep = self._enc_ps()
         mk_e = self.bytes(2, B, T * (2 * DIM + MLP_DIM)) if tr else None
         X1 = self.new(2, B, T, DIM)
         st = B * T * DIM
-        L.vc_hct_encoder_fwd(B, T, X0.data_ptr(), st, self.W["enc0"], self.W["enc1"], *ep, self.site_seed(2),
-                             X1.data_ptr(), st, mk_e.data_ptr() if tr else None, s)
+        seed = (ds.cur_ptr, 1000003 * 2) if ds is not None else (self.site_seed(2),)
+        (L.vc_hct_encoder_fwd_ds if ds is not None else L.vc_hct_encoder_fwd)(
+            B, T, X0.data_ptr(), st, self.W["enc0"], self.W["enc1"], *ep, *seed, X1.data_ptr(), st,
+            mk_e.data_ptr() if tr else None, s)
         # the cross-token step (:162-171), both directions in one launch; only the cls rows go on to the head
         cp = self._ct_ps()
         mk_c = self.bytes(2, B, HEADS * T + DIM) if tr else None
         C = self.new(2 * B, DIM)
-        L.vc_hct_ctattn_fwd(B, T, X1.data_ptr(), st, self.W["ct0"], self.W["ct1"], *cp, self.site_seed(3),
-                            C.data_ptr(), mk_c.data_ptr() if tr else None, s)
+        seed = (ds.cur_ptr, 1000003 * 3) if ds is not None else (self.site_seed(3),)
+        (L.vc_hct_ctattn_fwd_ds if ds is not None else L.vc_hct_ctattn_fwd)(
+            B, T, X1.data_ptr(), st, self.W["ct0"], self.W["ct1"], *cp, *seed, C.data_ptr(),
+            mk_c.data_ptr() if tr else None, s)
         # mlp_head on both cls rows (2 B rows), summed (:362-364)
         Yc, mu, rs = self.new(2 * B, DIM), self.new(2 * B), self.new(2 * B)
         L.vc_layernorm_fwd(2 * B, DIM, C.data_ptr(), DIM, P["mlp_head.0.weight"], P["mlp_head.0.bias"], LN_EPS,

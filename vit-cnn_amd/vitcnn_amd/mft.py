@@ -26,6 +26,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from . import seeds
 from ._lib import lib
 from .flat import F32, FlatParams
 from .fusatnet import _counters   # one zeroed arrival-counter array per (device, stream)
@@ -200,7 +201,10 @@ class _Program:
         self.P = {n: base + F32 * o for n, o in m._poff.items()}
         self.masks = {}
         self.seed = 0
-        if self.train and any(p > 0 for p in self._drop_ps()):
+        drops = self.train and any(p > 0 for p in self._drop_ps())
+        # a device-resident step seed (seeds.attach): nothing is drawn on the host, the _ds entry reads it there
+        self.dseed = seeds.state_for(m, self.dev) if drops else None
+        if drops and self.dseed is None:
             self.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             # data parallelism: every rank seeds torch alike, so mix the rank in -- the replicas must not apply
             # the same keep masks to their different shards
@@ -217,8 +221,12 @@ class _Program:
     def drop(self, site, x, add, y, n, p):
         """y = add + dropout_p(x) (add may be None, y may be x); the keep mask is saved under `site`"""
         mk = torch.empty(n, dtype=torch.uint8, device=self.dev)
-        self.L.vc_dropout_fwd(n, x.data_ptr(), add.data_ptr() if add is not None else None, y.data_ptr(),
-                              mk.data_ptr(), p, (self.seed + 1000003 * len(self.masks)) % (1 << 63), self.s)
+        if self.dseed is not None:
+            self.L.vc_dropout_fwd_ds(n, x.data_ptr(), add.data_ptr() if add is not None else None, y.data_ptr(),
+                                     mk.data_ptr(), p, self.dseed.cur_ptr, 1000003 * len(self.masks), self.s)
+        else:
+            self.L.vc_dropout_fwd(n, x.data_ptr(), add.data_ptr() if add is not None else None, y.data_ptr(),
+                                  mk.data_ptr(), p, (self.seed + 1000003 * len(self.masks)) % (1 << 63), self.s)
         self.masks[site] = mk
 
     def gemm(self, tA, tB, M, N, K, A, lda, Bm, ldb, C, ldc, bias=None, add=None, add_ld=0, bias_grad=None):

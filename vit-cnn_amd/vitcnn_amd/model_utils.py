@@ -283,20 +283,21 @@ def save_model(savename, model, model_name, dataset_name, train_state, type, **k
     return path
 
 
-def _stepper(net, optimizer, criterion):
+def _stepper(net, optimizer, criterion, capture_step=False):
     """the model's TrainStepper for this optimizer / criterion (kept across train() calls, so the
     captured per-shape graphs are reused)"""
     from .step import TrainStepper
     st = getattr(net, "_vc_stepper", None)
     if st is None or st.opt is not optimizer or st.crit is not criterion or \
+            st.capture_step != bool(capture_step) or \
             (st.exchange is None) == parallel.is_distributed():
-        st = TrainStepper(net, optimizer, criterion)
+        st = TrainStepper(net, optimizer, criterion, capture_step=capture_step)
         object.__setattr__(net, "_vc_stepper", st)
     return st
 
 
 def train(savename, run, bands, net, optimizer, criterion, data_loader, epoch, scheduler=None, display_iter=100,
-          device=torch.device("cpu"), display=None, val_loader=None, supervision="full"):
+          device=torch.device("cpu"), display=None, val_loader=None, supervision="full", capture_step=False):
     """Training loop of model_utils.py:854-1045: per batch one optimizer step (zero_grad, forward,
     criterion, backward, step: :916-934), the loss recorded per iteration (:936-938) and its running
     mean printed every `display_iter` iterations (:940-962), the scheduler stepped per epoch
@@ -304,7 +305,10 @@ def train(savename, run, bands, net, optimizer, criterion, data_loader, epoch, s
     is optional here.
 
     The step is `vitcnn_amd.step.TrainStepper.step`: for ViT-CNN with the fused AdamW one hipGraph
-    replay per batch (captured per batch shape; data parallel: bucketed RCCL all-reduce inside it).
+    replay per batch (captured per batch shape; data parallel: bucketed RCCL all-reduce inside it);
+    with `capture_step=True` also for the comparison models (MFT, HCTnet, MDL-RS, EndNet, SpectralFormer,
+    FusAtNet with the fused optimizer and the package's losses; the dropout masks' seed then lives in device memory
+    and every replay draws fresh masks: seeds.py).  `last_stats["launch"]` names the path.
     The per-iteration losses stay on the device and are read in one transfer at each display point
     and at the epoch end (the reference's `loss.item()` host sync per iteration would stall the queue
     every step); the recorded values are the same.
@@ -329,7 +333,7 @@ def train(savename, run, bands, net, optimizer, criterion, data_loader, epoch, s
         parallel.check_loader_shard(data_loader)  # a self-sharding loader (PatchBatcher) agrees with the group
         if not parallel.is_sharded(data_loader):
             data_loader = parallel.ShardedLoader(data_loader, parallel.rank(), parallel.world())
-    stepper = _stepper(net, optimizer, criterion)
+    stepper = _stepper(net, optimizer, criterion, capture_step)
     save_epoch = 16 if epoch == 128 else (epoch // 20 if epoch > 20 else 1)
     best_val_acc = 0.0
     best_model_wts = None
@@ -347,7 +351,7 @@ def train(savename, run, bands, net, optimizer, criterion, data_loader, epoch, s
         n_batches = len(data_loader)
         for batch_idx, (data, data2, target) in enumerate(data_loader):
             loss = stepper.step(data, data2, target)
-            if stepper.fused:
+            if stepper.replays:
                 loss = loss.clone()   # a replayed graph's loss buffer is overwritten by the next replay
             pending.append(loss.detach())
             nb += 1

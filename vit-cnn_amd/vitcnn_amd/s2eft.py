@@ -14,8 +14,10 @@ parameters live in one flat fp32 buffer whose `.grad` the backward fills (the fu
 Dropout (p = 0.1 in `get_model`) is applied in training at the reference's four sites (emb_dropout
 :151, to_out :43, FeedForward :26 and :28) by a counter-based hash mask (`vc_dropout_fwd`, seeded
 from torch's CPU generator each forward, so `torch.manual_seed` reproduces a run; a hipGraph replay
-repeats the captured masks).  The `mask` argument is unsupported (the reference's mask path
-references an un-imported `F`, :58, and raises too).
+repeats the captured masks unless a device-resident step seed is attached: `seeds.attach`, then the
+`_ds` entry points read the seed on the device and nothing is drawn on the host).  The `mask`
+argument is unsupported (the reference's mask path references an un-imported `F`, :58, and raises
+too).
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
+from . import seeds
 from ._lib import lib
 from .flat import F32, FlatParams
 
@@ -164,7 +167,10 @@ class _Program:
         self.keep = []
         self.pd = m.p_drop if m.training else 0.0
         self.pe = m.p_emb if m.training else 0.0
-        self.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (self.pd > 0 or self.pe > 0) else 0
+        # a device-resident step seed (seeds.attach): nothing is drawn on the host, the _ds entries read it there
+        self.dseed = seeds.state_for(m, self.dev) if (self.pd > 0 or self.pe > 0) else None
+        draw = (self.pd > 0 or self.pe > 0) and self.dseed is None
+        self.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if draw else 0
         if self.seed:
             # data parallelism: every rank seeds torch alike (main.py), so mix the rank in — the
             # replicas must not apply the same keep masks to their different shards
@@ -176,8 +182,12 @@ class _Program:
     def drop(self, site, x, add, y, n, p):
         """y = add + dropout_p(x) (add may be None); the keep mask is saved under `site`"""
         mk = torch.empty(n, dtype=torch.uint8, device=self.dev)
-        self.L.vc_dropout_fwd(n, x.data_ptr(), add.data_ptr() if add is not None else None, y.data_ptr(),
-                              mk.data_ptr(), p, (self.seed + 1000003 * len(self.masks)) % (1 << 63), self.s)
+        if self.dseed is not None:
+            self.L.vc_dropout_fwd_ds(n, x.data_ptr(), add.data_ptr() if add is not None else None, y.data_ptr(),
+                                     mk.data_ptr(), p, self.dseed.cur_ptr, 1000003 * len(self.masks), self.s)
+        else:
+            self.L.vc_dropout_fwd(n, x.data_ptr(), add.data_ptr() if add is not None else None, y.data_ptr(),
+                                  mk.data_ptr(), p, (self.seed + 1000003 * len(self.masks)) % (1 << 63), self.s)
         self.masks[site] = mk
 
     def new(self, *shape):

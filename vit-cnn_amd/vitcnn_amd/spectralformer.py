@@ -120,6 +120,12 @@ class _Program(s2eft._Program):
         if self.pe > 0:
             mk = torch.empty(B * T * D, dtype=torch.uint8, device=self.dev)
             self.masks["emb"] = mk    # site 0 of the seed sequence, as s2eft's drop("emb", ...)
+        if mk is not None and self.dseed is not None:   # the attached device seed, site offset 0
+            self.L.vc_sf_embed_fwd_ds(B, self.C1, self.C2, D, self.x1.data_ptr(), self.x2.data_ptr(),
+                                      P["patch_to_embedding.weight"], P["patch_to_embedding.bias"], P["cls_token"],
+                                      P["pos_embedding"], self.pe, self.dseed.cur_ptr, 0, X.data_ptr(), mk.data_ptr(),
+                                      self.s)
+            return X
         self.L.vc_sf_embed_fwd(B, self.C1, self.C2, D, self.x1.data_ptr(), self.x2.data_ptr(),
                                P["patch_to_embedding.weight"], P["patch_to_embedding.bias"], P["cls_token"],
                                P["pos_embedding"], self.pe, self.seed % (1 << 63), X.data_ptr(),

@@ -11,11 +11,13 @@ multi-stream step — forward, CE, backward and AdamW — into one hipGraph.
 """
 from __future__ import annotations
 
+import inspect
+
 import torch
 
-from . import parallel
-from .flat import expose_grad_views
-from .losses import CrossEntropyLoss, ce_forward_backward
+from . import parallel, seeds
+from .flat import FlatParams, expose_grad_views
+from .losses import Cross_fusion_CNN_Loss, CrossEntropyLoss, EndNet_Loss, ce_forward_backward
 from .model import Multimodality_Mamba, _Program
 from .optim import AdamW
 
@@ -73,6 +75,24 @@ class _Captured:
         self.grad = None
 
 
+def _capture_step_blocker(net, optimizer, criterion):
+    """why `capture_step=True` cannot capture this model / optimizer / criterion (None: it can)"""
+    if not isinstance(net, FlatParams) or isinstance(net, Multimodality_Mamba):
+        return "not one of the package's comparison models"
+    try:
+        params = [p for p in inspect.signature(net.forward).parameters.values()
+                  if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD) and p.default is p.empty]
+    except (TypeError, ValueError):
+        params = []
+    if len(params) != 2:
+        return "the model's forward does not take two inputs"
+    if not isinstance(optimizer, AdamW) or optimizer._owner() is not net:
+        return "the optimizer is not the package's fused AdamW / Adam over this model"
+    if not isinstance(criterion, (CrossEntropyLoss, Cross_fusion_CNN_Loss, EndNet_Loss)):
+        return "the criterion is not one of the package's losses"
+    return None
+
+
 class TrainStepper:
     """The optimizer step `model_utils.train` runs per batch (model_utils.py:918-934: zero_grad,
     forward, criterion, backward, step), as fast as the model allows:
@@ -88,11 +108,20 @@ class TrainStepper:
       so StepLR's lr changes take effect as with torch.optim.
     * anything else (torch modules / optimizers, S2EFT's one-input forward, FusAtNet): the reference's
       eager sequence, with `parallel.allreduce_gradients` between backward and step under DP.
+    * `capture_step=True` (opt-in): the comparison models -- a flat-parameter model other
+      than ViT-CNN with a two-input forward, stepped by the fused AdamW / Adam under one of the package's losses --
+      follow the same protocol through autograd: the first batch of a shape runs `zero_grad; crit(net(x1, x2),
+      t).backward(); opt.step()` eagerly, the second captures exactly that into a hipGraph, later ones copy into the
+      static inputs and replay.  The dropout masks' seed lives in device memory (`seeds.attach`; attached here from
+      torch's CPU generator if the model has dropout and none is attached) and `vc_seed_next` is the first launch
+      of every step, eager or replayed: step n uses `seeds.step_seed(base, n)` whichever way it ran, and a replay
+      draws fresh masks.  Under data parallelism this path is off: the eager sequence above, and `launch` says so.
 
-    `launch` says which path ran ("hipGraph", "eager", or the capture failure), never silently."""
+    `launch` says which path ran ("hipGraph", "eager", or why not / the capture failure), never silently."""
 
-    def __init__(self, net, optimizer, criterion, use_graph: bool = True):
+    def __init__(self, net, optimizer, criterion, use_graph: bool = True, capture_step: bool = False):
         self.net, self.opt, self.crit = net, optimizer, criterion
+        self.capture_step = bool(capture_step)
         self.fused = (isinstance(net, Multimodality_Mamba) and isinstance(optimizer, AdamW)
                       and isinstance(criterion, CrossEntropyLoss))
         self.use_graph = use_graph and self.fused
@@ -108,11 +137,40 @@ class TrainStepper:
                 # gloo's host-side collectives cannot be captured: the same fused step, eagerly
                 self.use_graph = False
                 self.launch = "eager (the gloo exchange is not graph-capturable)"
+        # the comparison models' captured step
+        self.generic = False
+        if self.capture_step and not self.fused:
+            why = _capture_step_blocker(net, optimizer, criterion)
+            if why is None and parallel.is_distributed():
+                why = "data parallel: the gradient all-reduce of this path is not captured"
+            if why is not None:
+                self.launch = f"eager (capture_step: {why})"
+            else:
+                self.generic = True
+                self.use_graph = bool(use_graph)
+                self.launch = "hipGraph" if self.use_graph else "eager"
+                self._drops = seeds.has_dropout(net)   # read once: a captured graph bakes every p in anyway
+
+    @property
+    def replays(self) -> bool:
+        """the returned loss may be a replayed graph's buffer, overwritten by the next step: clone it to keep it"""
+        return self.fused or self.generic
 
     def _check_binding(self):
         """captured graphs hold the parameter / buffer / optimizer-state addresses of their capture:
         drop them if the model was re-flattened (load_state_dict with assign, .to(), ...)"""
         m = self.net
+        if self.generic:
+            # FlatParams re-packs into a NEW flat buffer on every device move / parameter replacement (buffers move
+            # with it: nn.Module._apply), so its address stands for the module's storage; plus the optimizer state
+            # and the seed state the launches were recorded with
+            st = seeds.state(m)
+            key = (m._flat_store.data_ptr(), id(self.opt._dev["m"]) if self.opt._dev is not None else None,
+                   st.state_ptr if st is not None else None)
+            if key != self.binding:
+                self.graphs, self.seen = {}, set()
+                self.binding = key
+            return
         key = (m._bind_gen, m._flat_store.data_ptr(), m._bflat.data_ptr(), m._iflat.data_ptr(),
                id(self.opt._dev["m"]) if self.opt._dev is not None else None)
         if key != self.binding:
@@ -145,9 +203,74 @@ class TrainStepper:
         self.graphs[key] = c
         return c
 
+    def _autograd_step(self, st, data, data2, target):
+        """the reference sequence on the current stream, the seed advanced first; eager and captured alike"""
+        if st is not None:
+            st.advance()
+        loss = self.crit(self.net(data, data2), target)
+        loss.backward()
+        self.opt.step()
+        return loss.detach()
+
+    def _capture_generic(self, key, st, data, data2, target):
+        dev = data.device
+        c = _Captured(torch.empty_like(data, memory_format=torch.contiguous_format),
+                      torch.empty_like(data2, memory_format=torch.contiguous_format),
+                      torch.empty_like(target, memory_format=torch.contiguous_format))
+        torch.cuda.synchronize(dev)
+        self.opt.sync_hyper()          # nothing may change inside the capture (the optimizer's copy)
+        self.opt.zero_grad(set_to_none=True)
+        ctx = torch.cuda.graph(c.graph)
+        # the capture stream's arrival counters (cached per stream for the process) are created and zeroed now, not
+        # by a node of this graph: a capture that fails would otherwise leave them cached and never zeroed
+        from .fusatnet import _counters
+        _counters(dev, ctx.capture_stream.cuda_stream)
+        try:
+            with ctx:
+                c.loss = self._autograd_step(st, c.hsi, c.lidar, c.target)
+        except RuntimeError as e:    # reported through `launch`, and every shape stays eager
+            torch.cuda.synchronize(dev)
+            self.opt.zero_grad(set_to_none=True)
+            self.launch = f"eager (graph capture failed: {str(e)[:100]})"
+            self.use_graph = False
+            return None
+        c.grad = self.net.flat_params.grad
+        self.graphs[key] = c
+        return c
+
+    def _step_generic(self, data, data2, target):
+        net = self.net
+        dev = net.flat_params.device
+        data = data.to(dev, non_blocking=True)
+        data2 = data2.to(dev, non_blocking=True)
+        target = target.to(dev, non_blocking=True)
+        net._ensure_flat()
+        self.opt._device_state(net.flat_params)   # the optimizer state exists before the binding is taken
+        st = seeds.state(net)
+        if st is None and self._drops:
+            st = seeds.attach(net)
+        self._check_binding()
+        key = (tuple(data.shape), data.dtype, tuple(data2.shape), data2.dtype, tuple(target.shape), target.dtype)
+        c = self.graphs.get(key)
+        if c is None and self.use_graph and key in self.seen:
+            c = self._capture_generic(key, st, data, data2, target)
+        self.seen.add(key)
+        if c is None:
+            self.opt.zero_grad(set_to_none=True)
+            return self._autograd_step(st, data, data2, target)
+        c.hsi.copy_(data)
+        c.lidar.copy_(data2)
+        c.target.copy_(target)
+        self.opt.sync_hyper()
+        c.graph.replay()
+        net.flat_params.grad = c.grad
+        return c.loss
+
     def step(self, data, data2, target):
         """one optimizer step on this batch; returns the loss as a device scalar"""
         net = self.net
+        if self.generic:
+            return self._step_generic(data, data2, target)
         if not self.fused:
             self.opt.zero_grad()
             out = net(data, data2)
