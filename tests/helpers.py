@@ -1,4 +1,5 @@
 """Shared test helpers: hash-filled state dicts keyed by the reference's 1704 state_dict names."""
+import contextlib
 import json
 import os
 
@@ -48,6 +49,34 @@ def rel_err(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+@contextlib.contextmanager
+def program_spy(model_cls=None):
+    """Every program the comparison models' shared autograd Function creates inside the block (only those of
+    `model_cls` models, if given), in order of creation: `progs[i].masks` holds forward i's keep-mask tensors (inside
+    a capture: the graph's own buffers)."""
+    from vitcnn_amd.program import ProgramFunction
+    orig, progs = ProgramFunction.forward, []
+
+    def spy(ctx, model, flat, needs_grad, program, *xs):
+        def make(*args):
+            prog = program(*args)
+            if model_cls is None or isinstance(model, model_cls):
+                progs.append(prog)
+            return prog
+
+        return orig(ctx, model, flat, needs_grad, make, *xs)
+
+    ProgramFunction.forward = staticmethod(spy)
+    try:
+        yield progs
+    finally:
+        ProgramFunction.forward = staticmethod(orig)
+
+
+def cpu_masks(prog):
+    return {k: v.float().cpu() for k, v in prog.masks.items()}
 
 
 GUARD = 64        # elements of guard region after every kernel output of the per-kernel parity tests

@@ -23,6 +23,20 @@ def test_step_seed_is_deterministic_and_below_2_62():
     assert (1 << 62) - 1 + seeds.site_offset(64) < 1 << 63
 
 
+def test_host_seed_is_one_draw_with_the_rank_mixed_in(monkeypatch):
+    from vitcnn_amd import parallel, seeds
+    torch.manual_seed(5)
+    first = int(torch.randint(0, 2 ** 62, (1,)))
+    second = int(torch.randint(0, 2 ** 62, (1,)))
+    torch.manual_seed(5)
+    assert seeds.host_seed() == first                                   # rank 0: the draw itself
+    assert int(torch.randint(0, 2 ** 62, (1,))) == second               # exactly one draw was consumed
+    monkeypatch.setattr(parallel, "rank", lambda: 1)
+    torch.manual_seed(5)
+    assert seeds.host_seed() == (first + seeds.GOLDEN) % 2 ** 62
+    assert int(torch.randint(0, 2 ** 62, (1,))) == second
+
+
 def test_new_entry_points_parse_from_the_header():
     from vitcnn_amd._lib import parse_header
     sigs = parse_header()

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import program_spy
 from pixel_cases import spectralformer
 from seed_cases import HCT_ENC_SITE, hct_enc_attn_index, mix32_keep, within_bands
 
@@ -141,29 +142,6 @@ def test_stale_graphs_are_dropped_after_a_reflatten():
     assert torch.equal(la, lb) and torch.equal(pa, pb)
 
 
-class _MaskSpy:
-    """keeps the tensors of one site's mask bytes of every HCTnet forward (inside a capture: the graph's own buffer)"""
-
-    def __init__(self, site):
-        self.site, self.seen = site, []
-
-    def __enter__(self):
-        from vitcnn_amd.hctnet import _HCTFunction
-        self.fn, self.orig = _HCTFunction, _HCTFunction.forward
-        orig, seen, site = self.orig, self.seen, self.site
-
-        def spy(ctx, model, x1, x2, flat, needs_grad):
-            out = orig(ctx, model, x1, x2, flat, needs_grad)
-            seen.append(ctx.prog.masks[site])
-            return out
-
-        _HCTFunction.forward = staticmethod(spy)
-        return self
-
-    def __exit__(self, *exc):
-        self.fn.forward = staticmethod(self.orig)
-
-
 def test_replays_redraw_the_masks():
     _need_gpu()
     from vitcnn_amd import seeds
@@ -175,14 +153,14 @@ def test_replays_redraw_the_masks():
     stepper = TrainStepper(m, _optimizer("hct", m), _crit(), capture_step=True)
     batches = _batches("hct", 4, B)
     masks, steps = [], []
-    with _MaskSpy("enc.h.attn") as spy:
+    with program_spy(type(m)) as progs:   # every HCTnet forward's program (inside a capture: the graph's own buffers)
         for i, b in enumerate(batches):
             stepper.step(*b)
             torch.cuda.synchronize()
             steps.append(st.read()[1])
-            if i >= 1:     # steps 2, 3, 4 are replays of the graph captured at step 2: its mask buffer is spy.seen[1]
-                assert len(spy.seen) == 2
-                masks.append(spy.seen[1].cpu().numpy().copy())
+            if i >= 1:     # steps 2, 3, 4 are replays of the graph captured at step 2: its mask buffer is progs[1]'s
+                assert len(progs) == 2
+                masks.append(progs[1].masks["enc.h.attn"].cpu().numpy().copy())
     assert stepper.launch == "hipGraph" and len(stepper.graphs) == 1
     assert steps == [1, 2, 3, 4]
     assert masks[0].shape == (B, T, 64) and masks[0].size >= 4096
@@ -216,13 +194,13 @@ def test_a_plain_capture_repeats_its_masks():
     opt.sync_hyper()
     graph = torch.cuda.CUDAGraph()
     masks = []
-    with _MaskSpy("enc.h.attn") as spy:
+    with program_spy(type(m)) as progs:
         with torch.cuda.graph(graph):
             step()
         for _ in range(3):
             graph.replay()
             torch.cuda.synchronize()
-            masks.append(spy.seen[0].cpu().clone())
+            masks.append(progs[0].masks["enc.h.attn"].cpu().clone())
     assert 0 < int(masks[0].sum()) < masks[0].numel()
     assert torch.equal(masks[0], masks[1]) and torch.equal(masks[1], masks[2])
 

@@ -122,23 +122,12 @@ def test_hctnet_gpu_dropout_train():
     """dropout 0.1 at the reference's 12 sites: keep fraction ~0.9, logits and every gradient equal the oracle's
     evaluated with the HIP path's own keep masks; eval afterwards applies none"""
     _need_gpu()
-    from vitcnn_amd.hctnet import _HCTFunction
+    from helpers import cpu_masks, program_spy
     sd, run, _, t = golden("hctnet_a")
     m = _model(KW["hctnet_a"], sd, p_drop=0.1)
-    captured = {}
-    orig = _HCTFunction.forward
-
-    def spy(ctx, model, x1, x2, flat, needs_grad):
-        out = orig(ctx, model, x1, x2, flat, needs_grad)
-        captured["masks"] = {k: v.float().cpu() for k, v in ctx.prog.masks.items()}
-        return out
-
-    _HCTFunction.forward = staticmethod(spy)
-    try:
+    with program_spy(type(m)) as progs:
         got = _step(m, t["x1"], t["x2"], t["target"], t["weight"])
-    finally:
-        _HCTFunction.forward = staticmethod(orig)
-    masks = captured["masks"]
+    masks = cpu_masks(progs[-1])
     assert set(masks) == set(O.SITES) and len(masks) == 12
     keep = torch.cat([v.reshape(-1) for v in masks.values()])
     n = keep.numel()

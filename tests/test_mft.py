@@ -217,23 +217,12 @@ def test_mft_gpu_dropout_train():
     """dropout 0.1 at the reference's five sites: keep fraction ~0.9, logits and every gradient equal the oracle's
     evaluated with the HIP path's own keep masks; eval afterwards applies none"""
     _need_gpu()
-    from vitcnn_amd.mft import _MFTFunction
+    from helpers import cpu_masks, program_spy
     sd, run, _, t = _golden("mft_b4")
     m = _model(KW["mft_b4"], sd, p_drop=0.1)
-    captured = {}
-    orig = _MFTFunction.forward
-
-    def spy(ctx, model, x1, x2, flat, needs_grad):
-        out = orig(ctx, model, x1, x2, flat, needs_grad)
-        captured["masks"] = {k: v.float().cpu() for k, v in ctx.prog.masks.items()}
-        return out
-
-    _MFTFunction.forward = staticmethod(spy)
-    try:
+    with program_spy(type(m)) as progs:
         got = _step(m, t["x1"], t["x2"], t["target"], t["weight"])
-    finally:
-        _MFTFunction.forward = staticmethod(orig)
-    masks = captured["masks"]
+    masks = cpu_masks(progs[-1])
     assert set(masks) == {"emb"} | {f"{i}.{s}" for i in range(2) for s in ("attn", "ff1", "ff2")}
     keep = torch.cat(list(masks.values())).mean().item()
     assert 0.88 < keep < 0.92, keep

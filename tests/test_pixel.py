@@ -173,26 +173,15 @@ def test_spectralformer_gpu_b64_with_dropout_against_the_oracle_with_the_same_ma
     """get_model's configuration (dropout 0.1 at the embedding and the three sites of each layer): keep fraction ~0.9,
     and logits, loss and every gradient equal the oracle's evaluated with the HIP path's own keep masks"""
     _need_gpu()
-    from vitcnn_amd.spectralformer import _SpectralFormerFunction as Fn
+    from helpers import cpu_masks, program_spy
     torch.manual_seed(0)
     m = spectralformer(145, 16, dropout=0.1)
     sd = {k: v.clone() for k, v in m.state_dict().items()}
     x1, x2, t, w = _b64_inputs()
     m = m.to("cuda").train()
-    captured = {}
-    orig = Fn.forward
-
-    def spy(ctx, model, a, b, flat, needs_grad):
-        out = orig(ctx, model, a, b, flat, needs_grad)
-        captured["masks"] = {k: v.float().cpu() for k, v in ctx.prog.masks.items()}
-        return out
-
-    Fn.forward = staticmethod(spy)
-    try:
+    with program_spy(type(m)) as progs:
         _, ho, hloss, hg = _step(m, "SpectralFormer", x1, x2, t, w)
-    finally:
-        Fn.forward = staticmethod(orig)
-    masks = captured["masks"]
+    masks = cpu_masks(progs[-1])
     assert set(masks) == {"emb"} | {f"{i}.{s}" for i in range(5) for s in ("attn", "ff1", "ff2")}
     assert masks["emb"].numel() == 64 * 146 * 64
     keep = torch.cat(list(masks.values())).mean().item()

@@ -220,15 +220,15 @@ def existing_bn_bwd(L, c, train, B, K, N):
     """the existing backward of Linear + BatchNorm + ReLU on the same inputs: vc_bn_bwd_relu_ex (fed the float64
     pre-norm z, mean and rstd rounded to fp32; it recomputes the ReLU decisions from them) for dz, dgamma, dbeta, then
     the weight-gradient vc_gemm_ex with the bias gradient in its epilogue for dW, db"""
-    from vitcnn_amd.fusatnet import _counters
     from vitcnn_amd.model import N_COUNTERS
+    from vitcnn_amd.program import counters
     ref = c["ref"]
     d = lambda t: t.float().to(DEV).contiguous()
     x, dy, z, mean, rstd, gamma, beta = (d(t) for t in (c["x"], c["dy"], ref["z"], ref["mean"], ref["rstd"], c["gamma"],
                                                         c["beta"]))
     nws = 1 << 22
     ws = torch.empty(nws, device=DEV)
-    cnt = _counters(torch.device(DEV, torch.cuda.current_device()), S())
+    cnt = counters(torch.device(DEV, torch.cuda.current_device()), S())
     dz, dga, dbe = torch.empty(B, N, device=DEV), torch.empty(N, device=DEV), torch.empty(N, device=DEV)
     dW, db = torch.empty(N, K, device=DEV), torch.empty(N, device=DEV)
     L.vc_bn_bwd_relu_ex(train, B, N, dy.data_ptr(), N, z.data_ptr(), N, mean.data_ptr(), rstd.data_ptr(),

@@ -210,7 +210,8 @@ def test_s2eft_gpu_dropout_train():
     logits / every gradient equal the oracle's evaluated with the HIP path's own keep masks"""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    from vitcnn_amd.s2eft import ViT, _S2EFTFunction
+    from helpers import cpu_masks, program_spy
+    from vitcnn_amd.s2eft import ViT
     from vitcnn_amd.losses import CrossEntropyLoss
     z, sd, _ = _golden()
     kw = dict(KW, dropout=0.1, emb_dropout=0.1)
@@ -218,21 +219,10 @@ def test_s2eft_gpu_dropout_train():
     m.load_state_dict(sd)
     m = m.to("cuda").train()
     x, t, w = torch.from_numpy(z["x"]), torch.from_numpy(z["target"]), torch.from_numpy(z["weight"])
-    captured = {}
-    orig = _S2EFTFunction.forward
-
-    def spy(ctx, model, xx, flat, needs_grad):
-        out = orig(ctx, model, xx, flat, needs_grad)
-        captured["masks"] = {k: v.float().cpu() for k, v in ctx.prog.masks.items()}
-        return out
-
-    _S2EFTFunction.forward = staticmethod(spy)
-    try:
+    with program_spy(ViT) as progs:
         logits = m(x.cuda())
-    finally:
-        _S2EFTFunction.forward = staticmethod(orig)
     CrossEntropyLoss(weight=w.cuda())(logits, t.cuda()).backward()
-    masks = captured["masks"]
+    masks = cpu_masks(progs[-1])
     assert set(masks) == {"emb"} | {f"{i}.{s}" for i in range(5) for s in ("attn", "ff1", "ff2")}
     keep = torch.cat([v for v in masks.values()]).mean().item()
     assert 0.88 < keep < 0.92, keep

@@ -22,12 +22,11 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
-from .fusatnet import _counters   # one zeroed arrival-counter array per (device, stream)
 from .model import N_COUNTERS
 
-BN_MOMENTUM = 0.1
 FILTERS = (16, 32, 64, 128)
 C_MAX, NCLS_MAX = 512, 64           # bands per modality (the fused layer's K bound), classes
 TRAIN_B_MAX = 1024                  # VC_FC_TRAIN_BMAX (include/vitcnn.h)
@@ -79,11 +78,7 @@ class EndNet(FlatParams, nn.Module):
                              f"Linear + BatchNorm1d layer keeps the batch in LDS), got {B}")
         if not dev_ok:
             raise RuntimeError("EndNet MI355X path: inputs must be on a ROCm (cuda) device; no CPU fallback")
-        self._ensure_flat()
-        if self._flat_store.device != x1.device:
-            raise RuntimeError("model and inputs are on different devices")
-        needs_grad = torch.is_grad_enabled() and self._flat_store.requires_grad
-        out, de1, de2 = _EndNetFunction.apply(self, x1, x2, self._flat_store, needs_grad)
+        out, de1, de2 = program.run(self, _Program, x1, x2)
         return out, de1, de2, x1, x2
 
 
@@ -97,51 +92,22 @@ def _pixel_rows(x, C, name):
     return x.detach().to(torch.float32).contiguous()
 
 
-class _EndNetFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x1, x2, flat, needs_grad):
-        prog = _Program(model, x1, x2, needs_grad)
-        outs = prog.forward()
-        ctx.prog = prog if needs_grad else None
-        return outs
+class _Program(program.Program):
+    NAME = "EndNet"
 
-    @staticmethod
-    def backward(ctx, dout, dde1, dde2):
-        if ctx.prog is None:
-            raise RuntimeError("EndNet: backward through a forward run without grad")
-        prog, ctx.prog = ctx.prog, None
-        if prog.B > TRAIN_B_MAX:
-            raise RuntimeError(f"EndNet MI355X path: the backward takes at most {TRAIN_B_MAX} rows, got {prog.B}")
-        m = prog.m
-        ds = [torch.zeros(prog.B, n, dtype=torch.float32, device=prog.dev) if d is None
-              else d.detach().to(torch.float32).contiguous() for d, n in ((dout, m.ncls), (dde1, m.C1), (dde2, m.C2))]
-        return None, None, None, prog.backward(*ds), None
-
-
-class _Program:
-    """One forward (saving what the backward reads) and its hand-written backward, all on the current stream."""
-
-    SCRATCH = 1 << 22   # fp32 workspace of the data-gradient GEMMs (split-K slabs)
-
-    def __init__(self, m: EndNet, x1, x2, needs_grad=True):
-        self.m, self.L, self.dev = m, lib(), x1.device
-        self.needs_grad = needs_grad
-        self.s = torch.cuda.current_stream(self.dev).cuda_stream
-        self.x1, self.x2, self.B = x1, x2, x1.shape[0]
-        key = str(self.dev)
-        cache = m.__dict__.setdefault("_vc_scratch", {})
-        if key not in cache:
-            cache.clear()
-            cache[key] = torch.empty(self.SCRATCH, dtype=torch.float32, device=self.dev)
-        self.scr = cache[key]
-        self.cnt = _counters(self.dev, self.s)
-        self.train = m.training
-        base = m._flat_store.data_ptr()
-        self.P = {n: base + F32 * o for n, o in m._poff.items()}
+    def __init__(self, m: EndNet, needs_grad, x1, x2):
+        super().__init__(lib(), m, needs_grad, x1, x2)
+        self.x1, self.x2 = x1, x2
+        self.scratch(1 << 22)   # fp32 workspace of the data-gradient GEMMs (split-K slabs)
         self.mods = dict(m.named_children())
 
-    def new(self, *shape):
-        return torch.empty(*shape, dtype=torch.float32, device=self.dev)
+    def prepare_grads(self, grads):
+        """(dout, dde1, dde2); the gradient of an output the loss did not use is zero"""
+        if self.B > TRAIN_B_MAX:
+            raise RuntimeError(f"EndNet MI355X path: the backward takes at most {TRAIN_B_MAX} rows, got {self.B}")
+        m = self.m
+        return [torch.zeros(self.B, n, dtype=torch.float32, device=self.dev) if d is None
+                else d.detach().to(torch.float32).contiguous() for d, n in zip(grads, (m.ncls, m.C1, m.C2))]
 
     # ------------------------------------------------------------ one layer
     def fc(self, name, bn, mode, x, ldx, K, N, y=None, ldy=None):
@@ -156,13 +122,11 @@ class _Program:
         P = self.P
         if mode == FC_BN_RELU:
             mod = self.mods[bn]
-            mom = mod.momentum if mod.momentum is not None else BN_MOMENTUM
+            mom = self.bn_momentum(mod)
             xhat = st0 = st1 = None
             if self.train or self.needs_grad:   # what the backward reads (the train-mode kernel always writes it);
                 rec["xhat"], rec["st"] = self.new(B, N), self.new(2, N)   # eval with no backward to follow: nothing
                 xhat, st0, st1 = rec["xhat"].data_ptr(), rec["st"][0].data_ptr(), rec["st"][1].data_ptr()
-            if self.train:
-                self.nbt.append(mod.num_batches_tracked)
             self.L.vc_fc_fused_fwd(mode, 1 if self.train else 0, B, K, N, x, ldx, P[name + ".weight"], P[name + ".bias"],
                                    P[bn + ".weight"], P[bn + ".bias"], mod.running_mean.data_ptr(),
                                    mod.running_var.data_ptr(), mod.eps, mom, y, ldy, xhat, st0, st1, self.s)
@@ -187,9 +151,8 @@ class _Program:
                               None, None, 0, 0, 0, None, self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
 
     # ------------------------------------------------------------ forward
-    def forward(self):
+    def _forward(self):
         m, f = self.m, FILTERS
-        self.nbt = []
         joint = self.joint = self.new(self.B, 2 * f[3])      # cat([x1, x2], 1): the branches write its halves
         self.enc = {}
         for sfx, x, cin, half in (("_a", self.x1, m.C1, 0), ("_b", self.x2, m.C2, 1)):
@@ -212,8 +175,6 @@ class _Program:
                 recs.append(r)
                 ptr, ld = r["y"], r["ldy"]
             self.dec[sfx] = recs
-        if self.nbt:
-            torch._foreach_add_(self.nbt, 1)   # the ten applied BatchNorms, one multi-tensor launch
         return self.r7["buf"], self.dec["_a"][-1]["buf"], self.dec["_b"][-1]["buf"]
 
     # ------------------------------------------------------------ backward
@@ -221,10 +182,7 @@ class _Program:
         """the flat gradient of every parameter; each is written once (overwritten), the alignment gaps and the
         never-applied joint_encoder_bn7 stay zero"""
         m, f, B = self.m, FILTERS, self.B
-        grad = self.new(m._n_params)
-        self.L.vc_fill(m._n_params, grad.data_ptr(), 0.0, self.s)
-        gb = grad.data_ptr()
-        self.G = {n: gb + F32 * o for n, o in m._poff.items()}
+        grad = self.new_grad()
         d6 = self.new(B, f[2])
         self.fc_bwd(self.r7, dout.data_ptr(), m.ncls, d6.data_ptr(), f[2])
         d5 = self.new(B, f[3])          # joint_x feeds fc6 and both decoders: the first writes, the others add

@@ -29,6 +29,7 @@ import ctypes
 import torch
 import torch.nn as nn
 
+from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
 from .model import _IMPLICIT_CONV, N_COUNTERS
@@ -40,17 +41,8 @@ _TAP_CONV = True
 # take the pipelined conv (conv_tap.hip conv_pipe_ok: 16-B rows) instead of conv_tap
 _PAD_LIDAR = True
 
-BN_EPS, BN_MOMENTUM = 1e-5, 0.1
-_COUNTER_BUFS = {}
-
-
-def _counters(dev, stream):
-    """one zeroed arrival-counter array per (device, stream) (split-K in-launch combine, BN
-    reductions): kernels of one stream run in order and each leaves its counters zero"""
-    key = (dev.type, dev.index, stream)
-    if key not in _COUNTER_BUFS:
-        _COUNTER_BUFS[key] = torch.zeros(N_COUNTERS, dtype=torch.int32, device=dev)
-    return _COUNTER_BUFS[key].data_ptr()
+BN_EPS = 1e-5
+_counters = program.counters   # the pool's old name and home, kept importable
 
 
 class ConvUnit(nn.Module):
@@ -180,62 +172,30 @@ class FusAtNet(FlatParams, nn.Module):
             raise RuntimeError("FusAtNet needs patch >= 11 (five valid 3x3 convs + two 2x2 pools)")
         x1 = x1.detach().float().contiguous()
         x2 = x2.detach().float().contiguous()
-        self._ensure_flat()
-        if self._flat_store.device != x1.device:
-            raise RuntimeError("model and inputs are on different devices")
-        if torch.is_grad_enabled() and self._flat_store.requires_grad:
-            return _FusAtNetFunction.apply(self, x1, x2, self._flat_store)
-        with torch.no_grad():
-            return _Program(self, x1, x2, False).run()
+        return program.run(self, _Program, x1, x2)
 
 
-class _FusAtNetFunction(torch.autograd.Function):
+class _Program(program.Program):
     """Backward with out-of-place residual semantics (`b = relu(bn2(conv2(a))) + a`): the gradient the
     reference's code would have if its in-place `x += identity` (FusAtNet.py:44, :61) were written
     out of place -- the reference's own autograd raises there."""
 
-    @staticmethod
-    def forward(ctx, model, x1, x2, flat):
-        prog = _Program(model, x1, x2, True)
-        logits = prog.run()
-        ctx.prog = prog
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        grad = ctx.prog.backward(dlogits.detach().float().contiguous())
-        ctx.prog = None
-        return None, None, None, grad
-
-
-class _Program:
+    NAME = "FusAtNet"
     # split-K slabs of the tap-major conv GEMMs: ~50 MB at B = 64 (ADVICE r3: sized from the batch, not a
     # fixed 256 MiB), cached per (device, batch) on the model so a forward allocates nothing
     SCRATCH_PER_SAMPLE = 1 << 18      # floats (1 MiB) per sample: 64 MiB at B = 64
 
-    def __init__(self, m: FusAtNet, x1, x2, grad: bool):
-        self.m, self.L, self.dev = m, lib(), x1.device
-        self.s = torch.cuda.current_stream(self.dev).cuda_stream
-        self.B, self.P = x1.shape[0], x1.shape[2]
+    def __init__(self, m: FusAtNet, grad: bool, x1, x2):
+        super().__init__(lib(), m, grad, x1, x2)
+        self.Pp = x1.shape[2]
         self.x1, self.x2 = x1, x2
-        self.SCRATCH = max(1 << 22, self.B * self.SCRATCH_PER_SAMPLE)
-        key = (str(self.dev), self.SCRATCH)
-        cache = m.__dict__.setdefault("_vc_scratch", {})
-        if key not in cache:
-            cache.clear()
-            cache[key] = torch.empty(self.SCRATCH, dtype=torch.float32, device=self.dev)
-        self.scr = cache[key]
-        self.cnt = _counters(self.dev, self.s)
-        self.train = m.training
+        self.scratch(max(1 << 22, self.B * self.SCRATCH_PER_SAMPLE))
         self.grad = grad
         self.tape = []        # backward closures, run in reverse
         self.g = {}           # id(activation) -> gradient buffer (grad_of: zero-filled on creation;
                               # acc: left to its first writer, which writes it whole with beta 0)
         self.keep = {}        # id -> activation (keeps ids unique while the tape lives)
         self.no_grad_ids = set()
-
-    def new(self, *shape):
-        return torch.empty(*shape, dtype=torch.float32, device=self.dev)
 
     def grad_of(self, t):
         k = id(t)
@@ -349,13 +309,10 @@ class _Program:
 
     def bn_relu(self, y, M, C, bn, relu=1):
         mean, invstd = self.new(C), self.new(C)
-        if self.train:
-            self.nbt.append(bn.num_batches_tracked)   # incremented together at the end of run()
         z = self.new(*y.shape) if self.grad else y
         # train: statistics partials + the channel-tiled apply that reduces them (two launches)
-        self.L.vc_bn_forward_ex(1 if self.train else 0, M, C, y.data_ptr(), C, bn.eps,
-                                bn.momentum if bn.momentum is not None else BN_MOMENTUM, mean.data_ptr(),
-                                invstd.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+        self.L.vc_bn_forward_ex(1 if self.train else 0, M, C, y.data_ptr(), C, bn.eps, self.bn_momentum(bn),
+                                mean.data_ptr(), invstd.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
                                 bn.weight.data_ptr(), bn.bias.data_ptr(), relu, z.data_ptr(), C, self.scr.data_ptr(),
                                 self.SCRATCH, self.cnt, N_COUNTERS, self.s)
 
@@ -474,15 +431,8 @@ class _Program:
         self.L.vc_conv3x3_pack_many(n, ctypes.addressof(shapes), ctypes.addressof(src), ctypes.addressof(dst),
                                     self.s)
 
-    def run(self):
-        self.nbt = []
-        out = self._run()
-        if self.nbt:   # every executed BatchNorm's num_batches_tracked += 1: one multi-tensor launch
-            torch._foreach_add_(self.nbt, 1)
-        return out
-
-    def _run(self):
-        m, L, B, P = self.m, self.L, self.B, self.P
+    def _forward(self):
+        m, L, B, P = self.m, self.L, self.B, self.Pp
         self.pack_all()
         c1, c2 = m.c1, m.c2
         ld2 = (c2 + 3) // 4 * 4 if _PAD_LIDAR else c2

@@ -19,7 +19,7 @@ cls rows as 2 B rows.  The parameters live in one flat fp32 buffer whose `.grad`
 
 Dropout (12 sites, p = 0.1 in the reference: the two embeddings; per branch the attention output and the MLP twice; per
 direction the attention probabilities and to_out) is applied in training inside those kernels with `vc_dropout_fwd`'s
-hash, seeded and rank-mixed as in `s2eft.py`; each site's p is read from the module tree at forward time and every keep
+hash, seeded and rank-mixed by `program.py`; each site's p is read from the module tree at forward time and every keep
 mask is kept as bytes (`_Program.masks`).
 
 Patch sides 5..30: the tokeniser keeps a sample's L x (P-2)^2 softmax weights twice in LDS in its backward
@@ -30,14 +30,12 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import seeds
+from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
-from .fusatnet import _counters   # one zeroed arrival-counter array per (device, stream)
 from .model import N_COUNTERS
 
 LN_EPS = 1e-5        # nn.LayerNorm's default (HCTnet.py:35, :313)
-BN_MOMENTUM = 0.1
 DIM = 64
 HEADS = 8
 MLP_DIM = 8
@@ -180,13 +178,9 @@ class HCTnet(FlatParams, nn.Module):
             raise RuntimeError(f"expected x2 [B, {self.in_channels}, {P}, {P}] matching x1, got {list(x2.shape)}")
         if x1.shape[0] < 1:
             raise RuntimeError("empty batch")
-        self._ensure_flat()
-        if self._flat_store.device != x1.device:
-            raise RuntimeError("model and inputs are on different devices")
         x1 = x1.detach().to(torch.float32).contiguous()
         x2 = x2.detach().to(torch.float32).contiguous()
-        needs_grad = torch.is_grad_enabled() and self._flat_store.requires_grad
-        return _HCTFunction.apply(self, x1, x2, self._flat_store, needs_grad)
+        return program.run(self, _Program, x1, x2)
 
 
 def _check_supported(in_channels, num_classes, num_tokens, dim, heads, mlp_dim, h_dim, l_dim, depth, dropout,
@@ -246,58 +240,19 @@ def _packed_offsets(m):
     return out
 
 
-class _HCTFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x1, x2, flat, needs_grad):
-        prog = _Program(model, x1, x2, needs_grad)
-        logits = prog.forward()
-        ctx.prog = prog if needs_grad else None
-        return logits
+class _Program(program.Program):
+    NAME = "HCTnet"
 
-    @staticmethod
-    def backward(ctx, dlogits):
-        if ctx.prog is None:
-            raise RuntimeError("HCTnet: backward through a forward run without grad")
-        grad = ctx.prog.backward(dlogits.detach().to(torch.float32).contiguous())
-        ctx.prog = None
-        return None, None, None, grad, None
-
-
-class _Program:
-    """One forward (saving what the backward reads) and its hand-written backward, all on the current stream."""
-
-    def __init__(self, m: HCTnet, x1, x2, needs_grad):
-        self.m, self.L, self.dev = m, lib(), x1.device
-        self.s = torch.cuda.current_stream(self.dev).cuda_stream
+    def __init__(self, m: HCTnet, needs_grad, x1, x2):
+        super().__init__(lib(), m, needs_grad, x1, x2)
         self.x1, self.x2 = x1, x2
-        self.B, self.Pp = x1.shape[0], x1.shape[2]
-        B = self.B
+        self.Pp = x1.shape[2]
         # split-K slabs; with a backward to come, its per-sample weight-gradient partials (both cross-token
-        # directions are the largest)
-        self.SCRATCH = max(1 << 22, 2 * B * CT_FLOATS if needs_grad else 0)
-        cache = m.__dict__.setdefault("_vc_scratch", {})
-        key = str(self.dev)
-        if key not in cache or cache[key].numel() < self.SCRATCH:
-            cache.clear()
-            cache[key] = torch.empty(self.SCRATCH, dtype=torch.float32, device=self.dev)
-        self.scr = cache[key]
-        self.SCRATCH = self.scr.numel()
-        self.cnt = _counters(self.dev, self.s)
-        self.train = m.training
+        # directions are the largest).  Grow-only, and the kernels are told the buffer's own size
+        self.scratch(max(1 << 22, 2 * self.B * CT_FLOATS if needs_grad else 0), grow=True)
         base = m._flat_store.data_ptr()
-        self.P = {n: base + F32 * o for n, o in m._poff.items()}
         self.W = {k: base + F32 * o for k, o in m._packed.items()}
-        self.masks = {}
-        self.seed = 0
-        drops = self.train and any(p > 0 for p in self._drop_ps())
-        # a device-resident step seed (seeds.attach): nothing is drawn on the host, the _ds entries read it there
-        self.dseed = seeds.state_for(m, self.dev) if drops else None
-        if drops and self.dseed is None:
-            self.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            # data parallelism: every rank seeds torch alike, so mix the rank in -- the replicas must not apply
-            # the same keep masks to their different shards
-            from .parallel import rank
-            self.seed = (self.seed + 0x9E3779B97F4A7C15 * rank()) % (1 << 62)
+        self.seed_dropout(self.train and any(p > 0 for p in self._drop_ps()))
 
     def _enc_ps(self):
         """(attention output, MLP hidden, MLP output) p of both branches; 0 in eval"""
@@ -322,9 +277,6 @@ class _Program:
     def site_seed(self, k):
         return (self.seed + 1000003 * k) % (1 << 63)
 
-    def new(self, *shape):
-        return torch.empty(*shape, dtype=torch.float32, device=self.dev)
-
     def bytes(self, *shape):
         return torch.empty(*shape, dtype=torch.uint8, device=self.dev)
 
@@ -342,36 +294,7 @@ class _Program:
                              self.scr.data_ptr(), self.SCRATCH, self.s)
         return y, wt
 
-    def bn(self, pfx, mod, y, M, C):
-        """train-mode (batch statistics, running statistics updated) or eval-mode BatchNorm + ReLU of rows y"""
-        mean, invstd, z = self.new(C), self.new(C), self.new(M, C)
-        if self.train:
-            self.nbt.append(mod.num_batches_tracked)
-        self.L.vc_bn_forward_ex(1 if self.train else 0, M, C, y.data_ptr(), C, mod.eps,
-                                mod.momentum if mod.momentum is not None else BN_MOMENTUM, mean.data_ptr(),
-                                invstd.data_ptr(), mod.running_mean.data_ptr(), mod.running_var.data_ptr(),
-                                self.P[pfx + ".weight"], self.P[pfx + ".bias"], 1, z.data_ptr(), C,
-                                self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
-        return z, mean, invstd
-
-    def rows(self, x, C, HW):
-        """NCHW -> channels-last rows padded to a multiple of 4 floats (zero-filled)"""
-        ld = (C + 3) // 4 * 4
-        y = self.new(self.B * HW, ld)
-        if ld == C:
-            self.L.vc_nchw_to_nhwc(self.B, C, HW, x.data_ptr(), y.data_ptr(), self.s)
-        else:
-            self.L.vc_nchw_to_nhwc_pad(self.B, C, HW, x.data_ptr(), y.data_ptr(), ld, self.s)
-        return y, ld
-
     # ------------------------------------------------------------ forward
-    def forward(self):
-        self.nbt = []
-        out = self._forward()
-        if self.nbt:   # every BatchNorm's num_batches_tracked += 1: one multi-tensor launch
-            torch._foreach_add_(self.nbt, 1)
-        return out
-
     def _forward(self):
         m, L, B, Pp, P, s = self.m, self.L, self.B, self.Pp, self.P, self.s
         H1, H2 = Pp - 2, Pp - 4
@@ -461,11 +384,9 @@ class _Program:
         scr, ns = self.scr.data_ptr(), self.SCRATCH
         sv = self.sv
         tr = 1 if self.train else 0
-        grad = self.new(m._n_params)
-        L.vc_fill(m._n_params, grad.data_ptr(), 0.0, s)
-        gb = grad.data_ptr()
-        G = {k: gb + F32 * o for k, o in m._poff.items()}
-        GW = {k: gb + F32 * o for k, o in m._packed.items()}
+        grad = self.new_grad()
+        G = self.G
+        GW = {k: grad.data_ptr() + F32 * o for k, o in m._packed.items()}
 
         def ptr(t):
             return t.data_ptr() if t is not None else None

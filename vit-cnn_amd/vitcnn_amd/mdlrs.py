@@ -27,12 +27,11 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
-from .fusatnet import _counters   # one zeroed arrival-counter array per (device, stream)
 from .model import N_COUNTERS
 
-BN_MOMENTUM = 0.1
 FILTERS = (16, 32, 64, 128)     # n1 = 16: conv1, conv2, conv3 (= conv6), conv4 (= conv5) output widths
 P_MIN, P_MAX = 3, 32            # a 3x3 conv needs a 3x3 map; the pooled maps of larger patches are untested
 C1_MAX, C2_MAX, NCLS_MAX = 512, 8, 64   # the envelope the tests cover
@@ -104,13 +103,9 @@ class _MDLRS(FlatParams, nn.Module):
             raise RuntimeError(f"expected x2 [B, {self.C2}, P, P] matching x1, got {list(x2.shape)}")
         if not P_MIN <= x1.shape[2] <= P_MAX:
             raise RuntimeError(f"{name} MI355X path: patch_size must be in {P_MIN}..{P_MAX}, got {x1.shape[2]}")
-        self._ensure_flat()
-        if self._flat_store.device != x1.device:
-            raise RuntimeError("model and inputs are on different devices")
         x1 = x1.detach().to(torch.float32).contiguous()
         x2 = x2.detach().to(torch.float32).contiguous()
-        needs_grad = torch.is_grad_enabled() and self._flat_store.requires_grad
-        out = _MDLRSFunction.apply(self, x1, x2, self._flat_store, needs_grad)
+        out = program.run(self, _Program, x1, x2)
         return out if self.KIND == "cross" else out[0]
 
 
@@ -149,57 +144,28 @@ class Cross_fusion_CNN(_MDLRS):
     _layers = _two_branch_layers
 
 
-class _MDLRSFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x1, x2, flat, needs_grad):
-        prog = _Program(model, x1, x2)
-        logits = prog.forward()                    # [G, B, ncls]
-        ctx.prog = prog if needs_grad else None
-        return tuple(logits.unbind(0))
+class _Program(program.Program):
+    NAME = "MDL-RS"
 
-    @staticmethod
-    def backward(ctx, *dlogits):
-        if ctx.prog is None:
-            raise RuntimeError("MDL-RS: backward through a forward run without grad")
-        prog, ctx.prog = ctx.prog, None
-        B, ncls = prog.B, prog.m.ncls
-        ds = [torch.zeros(B, ncls, dtype=torch.float32, device=prog.dev) if d is None
-              else d.detach().to(torch.float32).contiguous() for d in dlogits]
-        step, base = B * ncls * F32, ds[0].untyped_storage().data_ptr()
-        if all(d.data_ptr() == ds[0].data_ptr() + i * step and d.untyped_storage().data_ptr() == base
-               for i, d in enumerate(ds)):
-            dl = ds[0]      # side by side in one buffer (Cross_fusion_CNN_Loss writes them so): no copy
-        else:
-            dl = torch.stack(ds)
-        return None, None, None, prog.backward(dl), None
-
-
-class _Program:
-    """One forward (saving what the backward reads) and its hand-written backward, all on the current stream."""
-
-    SCRATCH = 1 << 22   # fp32 workspace: split-K slabs, BatchNorm / conv partial sums
-
-    def __init__(self, m: _MDLRS, x1, x2):
-        self.m, self.L, self.dev = m, lib(), x1.device
-        self.s = torch.cuda.current_stream(self.dev).cuda_stream
+    def __init__(self, m: _MDLRS, needs_grad, x1, x2):
+        super().__init__(lib(), m, needs_grad, x1, x2)
         self.x1, self.x2 = x1, x2
-        self.B, self.Pp = x1.shape[0], x1.shape[2]
-        key = str(self.dev)
-        cache = m.__dict__.setdefault("_vc_scratch", {})
-        if key not in cache:
-            cache.clear()
-            cache[key] = torch.empty(self.SCRATCH, dtype=torch.float32, device=self.dev)
-        self.scr = cache[key]
-        self.cnt = _counters(self.dev, self.s)
-        self.train = m.training
-        base = m._flat_store.data_ptr()
-        self.P = {n: base + F32 * o for n, o in m._poff.items()}
+        self.Pp = x1.shape[2]
+        self.scratch(1 << 22)   # fp32 workspace: split-K slabs, BatchNorm / conv partial sums
         self.mods = dict(m.named_children())
         self.H2 = self.Pp // 2 + 1     # after the first pool
         self.H3 = self.H2 // 2 + 1     # after the second
 
-    def new(self, *shape):
-        return torch.empty(*shape, dtype=torch.float32, device=self.dev)
+    def prepare_grads(self, dlogits):
+        """[G, B, ncls] in one buffer; the gradient of an output the loss did not use is zero"""
+        B, ncls = self.B, self.m.ncls
+        ds = [torch.zeros(B, ncls, dtype=torch.float32, device=self.dev) if d is None
+              else d.detach().to(torch.float32).contiguous() for d in dlogits]
+        step, base = B * ncls * F32, ds[0].untyped_storage().data_ptr()
+        if all(d.data_ptr() == ds[0].data_ptr() + i * step and d.untyped_storage().data_ptr() == base
+               for i, d in enumerate(ds)):
+            return [ds[0]]      # side by side in one buffer (Cross_fusion_CNN_Loss writes them so): no copy
+        return [torch.stack(ds)]
 
     # ------------------------------------------------------------ primitives
     def gemm(self, tA, tB, M, N, K, A, lda, Bm, ldb, C, ldc, bias=None, bias_grad=None, beta=0.0):
@@ -232,9 +198,7 @@ class _Program:
 
     def _bn_mod(self, name):
         mod = self.mods[name]
-        if self.train:
-            self.nbt.append(mod.num_batches_tracked)
-        return mod, (mod.momentum if mod.momentum is not None else BN_MOMENTUM)
+        return mod, self.bn_momentum(mod)
 
     def bn_relu(self, name, y, M, C, z):
         """z (ptr, ld C) = relu(BatchNorm(y [M, C])): batch statistics and running-statistics update in training"""
@@ -408,18 +372,17 @@ class _Program:
                                    self.G["conv7.weight"], self.G["conv7.bias"], self.s)
 
     # ------------------------------------------------------------ forward
-    def forward(self):
-        self.nbt = []
-        out = getattr(self, "_fwd_" + self.m.KIND)()
-        if self.nbt:
-            # num_batches_tracked += the number of applications, one multi-tensor launch per distinct count (a
-            # BatchNorm Cross_fusion_CNN applies two or three times appears once in each list)
-            count = {}
-            for t in self.nbt:
-                count[id(t)] = (t, count.get(id(t), (t, 0))[1] + 1)
-            for n in sorted({c for _, c in count.values()}):
-                torch._foreach_add_([t for t, c in count.values() if c == n], n)
-        return out
+    def _forward(self):
+        return tuple(getattr(self, "_fwd_" + self.m.KIND)().unbind(0))    # [G, B, ncls] -> G outputs
+
+    def count_batches(self):
+        # num_batches_tracked += the number of applications, one multi-tensor launch per distinct count (a
+        # BatchNorm Cross_fusion_CNN applies two or three times appears once in each list)
+        count = {}
+        for t in self.nbt:
+            count[id(t)] = (t, count.get(id(t), (t, 0))[1] + 1)
+        for n in sorted({c for _, c in count.values()}):
+            torch._foreach_add_([t for t, c in count.values() if c == n], n)
 
     def _fwd_early(self):
         f = FILTERS
@@ -499,12 +462,8 @@ class _Program:
     # ------------------------------------------------------------ backward
     def backward(self, dlogits):
         """the flat gradient of every parameter; each is written once (overwritten), the alignment gaps stay zero"""
-        m = self.m
-        grad = self.new(m._n_params)
-        self.L.vc_fill(m._n_params, grad.data_ptr(), 0.0, self.s)
-        gb = grad.data_ptr()
-        self.G = {n: gb + F32 * o for n, o in m._poff.items()}
-        getattr(self, "_bwd_" + m.KIND)(dlogits)
+        grad = self.new_grad()
+        getattr(self, "_bwd_" + self.m.KIND)(dlogits)
         self.a = self.b = self.c = self.x4 = self.hd = self.x3 = self.p4 = None
         return grad
 

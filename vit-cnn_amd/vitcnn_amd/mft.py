@@ -18,7 +18,7 @@ flat fp32 buffer whose `.grad` the backward fills:
 * the tokenisers, the single-query cross attention and the broadcast residual are `vc_mft_*` kernels.
 
 Dropout (p = 0.1, hard-coded in the reference; five sites: the embeddings :210, proj_drop :58, the Mlp's
-dropout twice :81, :83) is applied in training by `vc_dropout_fwd`, seeded and rank-mixed as in `s2eft.py`;
+dropout twice :81, :83) is applied in training by `vc_dropout_fwd`, seeded and rank-mixed by `program.py`;
 each site's p is read from the module tree at forward time.  `HSIOnly` is stored and unused, as in the reference.
 """
 from __future__ import annotations
@@ -26,14 +26,12 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import seeds
+from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
-from .fusatnet import _counters   # one zeroed arrival-counter array per (device, stream)
 from .model import N_COUNTERS
 
 LN_EPS = 1e-6        # LayerNorm(dim, eps=1e-6) (MFT.py:91-92, :117)
-BN_MOMENTUM = 0.1
 DIM = 64             # FM * 4 with FM = 16: the tokenisers' 64 is hard-coded in the reference (:164-176)
 HEADS = 8
 TOKENS = 5           # 1 LiDAR token + 4 HSI tokens
@@ -136,14 +134,10 @@ class MFT(FlatParams, nn.Module):
             raise RuntimeError(f"expected x1 [B, {self.NC}, {P}, {P}], got {list(x1.shape)}")
         if x2.dim() < 2 or x2.shape[0] != x1.shape[0] or x2[0].numel() != self.NCLidar * P * P:
             raise RuntimeError(f"expected x2 [B, {self.NCLidar}, {P}, {P}] matching x1, got {list(x2.shape)}")
-        self._ensure_flat()
-        if self._flat_store.device != x1.device:
-            raise RuntimeError("model and inputs are on different devices")
         B = x1.shape[0]
         x1 = x1.detach().to(torch.float32).reshape(B, self.NC, P, P).contiguous()      # the reshapes of :179-181
         x2 = x2.detach().to(torch.float32).reshape(B, self.NCLidar, P, P).contiguous()
-        needs_grad = torch.is_grad_enabled() and self._flat_store.requires_grad
-        return _MFTFunction.apply(self, x1, x2, self._flat_store, needs_grad)
+        return program.run(self, _Program, x1, x2)
 
 
 def _check_supported(patch_size, FM, NC, NCLidar, Classes):
@@ -160,105 +154,29 @@ def _check_supported(patch_size, FM, NC, NCLidar, Classes):
         raise ValueError("MFT: NCLidar and Classes must be positive")
 
 
-class _MFTFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x1, x2, flat, needs_grad):
-        prog = _Program(model, x1, x2)
-        logits = prog.forward()
-        ctx.prog = prog if needs_grad else None
-        return logits
+class _Program(program.Program):
+    NAME = "MFT"
+    D, LN_EPS = DIM, LN_EPS     # what program.Program.ln reads
 
-    @staticmethod
-    def backward(ctx, dlogits):
-        if ctx.prog is None:
-            raise RuntimeError("MFT: backward through a forward run without grad")
-        grad = ctx.prog.backward(dlogits.detach().to(torch.float32).contiguous())
-        ctx.prog = None
-        return None, None, None, grad, None
-
-
-class _Program:
-    """One forward (saving what the backward reads) and its hand-written backward, all on the current stream."""
-
-    def __init__(self, m: MFT, x1, x2):
-        self.m, self.L, self.dev = m, lib(), x1.device
-        self.s = torch.cuda.current_stream(self.dev).cuda_stream
+    def __init__(self, m: MFT, needs_grad, x1, x2):
+        super().__init__(lib(), m, needs_grad, x1, x2)
         self.x1, self.x2 = x1, x2
-        self.B, self.Pp = x1.shape[0], m.patchsize
+        self.Pp = m.patchsize
         B = self.B
         # fixed-order partial sums (conv5's weight gradient, the tokenisers, the attention core), split-K slabs
-        self.SCRATCH = max(1 << 22, self.L.vc_mft_conv3d_ws_floats(B, m.NC, self.Pp),
-                           B * (4 * DIM + DIM * DIM), B * 3 * DIM * 8)
-        key = (str(self.dev), self.SCRATCH)
-        cache = m.__dict__.setdefault("_vc_scratch", {})
-        if key not in cache:
-            cache.clear()
-            cache[key] = torch.empty(self.SCRATCH, dtype=torch.float32, device=self.dev)
-        self.scr = cache[key]
-        self.cnt = _counters(self.dev, self.s)
-        self.train = m.training
-        base = m._flat_store.data_ptr()
-        self.P = {n: base + F32 * o for n, o in m._poff.items()}
-        self.masks = {}
-        self.seed = 0
-        drops = self.train and any(p > 0 for p in self._drop_ps())
-        # a device-resident step seed (seeds.attach): nothing is drawn on the host, the _ds entry reads it there
-        self.dseed = seeds.state_for(m, self.dev) if drops else None
-        if drops and self.dseed is None:
-            self.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            # data parallelism: every rank seeds torch alike, so mix the rank in -- the replicas must not apply
-            # the same keep masks to their different shards
-            from .parallel import rank
-            self.seed = (self.seed + 0x9E3779B97F4A7C15 * rank()) % (1 << 62)
+        self.scratch(max(1 << 22, self.L.vc_mft_conv3d_ws_floats(B, m.NC, self.Pp),
+                         B * (4 * DIM + DIM * DIM), B * 3 * DIM * 8))
+        self.seed_dropout(self.train and any(p > 0 for p in self._drop_ps()))
 
     def _drop_ps(self):
         m = self.m
         return [m.dropout.p] + [p for blk in m.ca.layer for p in (blk.attn.proj_drop.p, blk.ffn.dropout.p)]
 
-    def new(self, *shape):
-        return torch.empty(*shape, dtype=torch.float32, device=self.dev)
-
-    def drop(self, site, x, add, y, n, p):
-        """y = add + dropout_p(x) (add may be None, y may be x); the keep mask is saved under `site`"""
-        mk = torch.empty(n, dtype=torch.uint8, device=self.dev)
-        if self.dseed is not None:
-            self.L.vc_dropout_fwd_ds(n, x.data_ptr(), add.data_ptr() if add is not None else None, y.data_ptr(),
-                                     mk.data_ptr(), p, self.dseed.cur_ptr, 1000003 * len(self.masks), self.s)
-        else:
-            self.L.vc_dropout_fwd(n, x.data_ptr(), add.data_ptr() if add is not None else None, y.data_ptr(),
-                                  mk.data_ptr(), p, (self.seed + 1000003 * len(self.masks)) % (1 << 63), self.s)
-        self.masks[site] = mk
-
     def gemm(self, tA, tB, M, N, K, A, lda, Bm, ldb, C, ldc, bias=None, add=None, add_ld=0, bias_grad=None):
         self.L.vc_gemm_ex(tA, tB, M, N, K, 1.0, A, lda, 0, Bm, ldb, 0, 0.0, C, ldc, 0, 1, bias, add, add_ld, 0, 0,
                           bias_grad, self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
 
-    def ln(self, pfx, X, R, ldx):
-        Y, mu, rs = self.new(R, DIM), self.new(R), self.new(R)
-        self.L.vc_layernorm_fwd(R, DIM, X, ldx, self.P[pfx + ".weight"], self.P[pfx + ".bias"], LN_EPS, Y.data_ptr(),
-                                DIM, mu.data_ptr(), rs.data_ptr(), self.s)
-        return Y, mu, rs
-
-    def bn(self, pfx, mod, y, M, C, relu):
-        """train-mode (batch statistics, running statistics updated) or eval-mode BatchNorm (+ ReLU) of rows y"""
-        mean, invstd, z = self.new(C), self.new(C), self.new(M * C)
-        if self.train:
-            self.nbt.append(mod.num_batches_tracked)
-        self.L.vc_bn_forward_ex(1 if self.train else 0, M, C, y.data_ptr(), C, mod.eps,
-                                mod.momentum if mod.momentum is not None else BN_MOMENTUM, mean.data_ptr(),
-                                invstd.data_ptr(), mod.running_mean.data_ptr(), mod.running_var.data_ptr(),
-                                self.P[pfx + ".weight"], self.P[pfx + ".bias"], relu, z.data_ptr(), C,
-                                self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
-        return z, mean, invstd
-
     # ------------------------------------------------------------ forward
-    def forward(self):
-        self.nbt = []
-        out = self._forward()
-        if self.nbt:   # every BatchNorm's num_batches_tracked += 1: one multi-tensor launch
-            torch._foreach_add_(self.nbt, 1)
-        return out
-
     def _forward(self):
         m, L, B, Pp, P, s = self.m, self.L, self.B, self.Pp, self.P, self.s
         HW = Pp * Pp
@@ -269,12 +187,7 @@ class _Program:
         sv = self.sv = {}
         # LiDAR branch (:153-157, :186-188): conv3x3 + BatchNorm + GELU over rows padded to 4 floats
         c2 = m.NCLidar
-        ld2 = (c2 + 3) // 4 * 4
-        x2r = self.new(M, ld2)
-        if ld2 == c2:
-            L.vc_nchw_to_nhwc(B, c2, HW, self.x2.data_ptr(), x2r.data_ptr(), s)
-        else:
-            L.vc_nchw_to_nhwc_pad(B, c2, HW, self.x2.data_ptr(), x2r.data_ptr(), ld2, s)
+        x2r, ld2 = self.rows(self.x2, c2, HW)
         wl = self.new(DIM * 9 * ld2)
         L.vc_conv3x3_pack(DIM, c2, 0, P["lidarConv.0.weight"], wl.data_ptr(), 0.0, s)
         yl = self.new(M, DIM)
@@ -369,10 +282,8 @@ class _Program:
         scr, ns = self.scr.data_ptr(), self.SCRATCH
         sv = self.sv
         tr = 1 if self.train else 0
-        grad = self.new(m._n_params)
-        L.vc_fill(m._n_params, grad.data_ptr(), 0.0, s)
-        gb = grad.data_ptr()
-        G = {n: gb + F32 * o for n, o in m._poff.items()}
+        grad = self.new_grad()
+        G = self.G
         # head
         Xout, Yc, muc, rsc = self.head
         self.gemm(1, 0, m.ncls, DIM, B, dlogits.data_ptr(), m.ncls, Yc.data_ptr(), DIM, G["out3.weight"], DIM,

@@ -689,7 +689,7 @@ class _Program:
 
     def wait(self, *events):
         """The current lane waits for the given events.  Capture rules this ROCm release needs
-        (tools/graph_probe*.py): a side lane is forked by waiting on a lane-0 event before it waits
+        (found by capturing small stream topologies one at a time): a side lane is forked by waiting on a lane-0 event before it waits
         on another side lane's event, and a lane never waits on its own event (a no-op anyway)."""
         for e in events:
             src = self._ev_lane.get(id(e))
@@ -1214,7 +1214,7 @@ class _Program:
         Lane 0 runs the global (hsiMamba) chain, lane 1 the GLfusion/non-local, local-conv and channel
         chains; the accumulations into dX are ordered local -> channel (lane 1) -> global (lane 0).
         Side lanes only ever wait on lane-0 events and lane 0 joins them (a star): the one cross-
-        stream topology this ROCm release's graph capture handles in a backward (tools/graph_probe.py)."""
+        stream topology this ROCm release's graph capture handles in a backward (see `wait`)."""
         B, ws, P, G = self.B, self.ws, self.P, self.G
         Cin, Cout, E = blk.cin, blk.cout, blk.embed
         D, R = E // 2, math.ceil(E / 16)

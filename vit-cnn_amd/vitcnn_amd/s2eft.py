@@ -27,7 +27,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from . import seeds
+from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
 
@@ -114,29 +114,7 @@ class ViT(FlatParams, nn.Module):
             raise RuntimeError("S2EFT MI355X path: input must be on a ROCm (cuda) device; no CPU fallback")
         if x.dim() != 3 or x.shape[1] != self.N or x.shape[2] != self.C:
             raise RuntimeError(f"expected x [B, {self.N}, {self.C}], got {list(x.shape)}")
-        self._ensure_flat()
-        if self._flat_store.device != x.device:
-            raise RuntimeError("model and input are on different devices")
-        x = x.detach().to(torch.float32).contiguous()
-        needs_grad = torch.is_grad_enabled() and self._flat_store.requires_grad
-        return _S2EFTFunction.apply(self, x, self._flat_store, needs_grad)
-
-
-class _S2EFTFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x, flat, needs_grad):
-        prog = _Program(model, x)
-        logits = prog.forward()
-        ctx.prog = prog if needs_grad else None
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        if ctx.prog is None:
-            raise RuntimeError("S2EFT: backward through a forward run without grad")
-        grad = ctx.prog.backward(dlogits.detach().to(torch.float32).contiguous())
-        ctx.prog = None
-        return None, None, grad, None
+        return program.run(self, _Program, x.detach().to(torch.float32).contiguous())
 
 
 # the backward's parameter gradients (round 6): 0 = each on the chain where its inputs are made; 1 = each on a side
@@ -150,48 +128,22 @@ _SIDE_STREAM = 3
 GEMM_GROUP_BYTES = 16384   # VC_GEMM_GROUP_BYTES (include/vitcnn.h)
 
 
-class _Program:
-    """One forward (saving what the backward reads) and its hand-written backward."""
+class _Program(program.Program):
+    NAME = "S2EFT"
+    COUNTERS = False    # vc_gemm keeps its split-K partials in the workspace: no arrival counters
+    SCRATCH = 1 << 22   # a new workspace per forward (and one more per backward on the side stream)
+    LN_EPS = LN_EPS
 
-    SCRATCH = 1 << 22
-
-    def __init__(self, m: ViT, x: torch.Tensor):
-        self.m, self.x, self.L = m, x, lib()
-        self.dev = x.device
-        self.s = torch.cuda.current_stream(self.dev).cuda_stream
-        self.B = x.shape[0]
-        self.T = m.N + 1
-        base = m._flat_store.data_ptr()
-        self.P = {n: base + F32 * o for n, o in m._poff.items()}
+    def __init__(self, m: ViT, needs_grad, x: torch.Tensor):
+        super().__init__(lib(), m, needs_grad, x)
+        self.x = x
+        self.T, self.D = m.N + 1, m.D
         self.scr = self.new(self.SCRATCH)
         self.keep = []
         self.pd = m.p_drop if m.training else 0.0
         self.pe = m.p_emb if m.training else 0.0
-        # a device-resident step seed (seeds.attach): nothing is drawn on the host, the _ds entries read it there
-        self.dseed = seeds.state_for(m, self.dev) if (self.pd > 0 or self.pe > 0) else None
-        draw = (self.pd > 0 or self.pe > 0) and self.dseed is None
-        self.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if draw else 0
-        if self.seed:
-            # data parallelism: every rank seeds torch alike (main.py), so mix the rank in — the
-            # replicas must not apply the same keep masks to their different shards
-            from .parallel import rank
-            self.seed = (self.seed + 0x9E3779B97F4A7C15 * rank()) % (1 << 62)
-        self.masks = {}
+        self.seed_dropout(self.pd > 0 or self.pe > 0)
         self._group = None
-
-    def drop(self, site, x, add, y, n, p):
-        """y = add + dropout_p(x) (add may be None); the keep mask is saved under `site`"""
-        mk = torch.empty(n, dtype=torch.uint8, device=self.dev)
-        if self.dseed is not None:
-            self.L.vc_dropout_fwd_ds(n, x.data_ptr(), add.data_ptr() if add is not None else None, y.data_ptr(),
-                                     mk.data_ptr(), p, self.dseed.cur_ptr, 1000003 * len(self.masks), self.s)
-        else:
-            self.L.vc_dropout_fwd(n, x.data_ptr(), add.data_ptr() if add is not None else None, y.data_ptr(),
-                                  mk.data_ptr(), p, (self.seed + 1000003 * len(self.masks)) % (1 << 63), self.s)
-        self.masks[site] = mk
-
-    def new(self, *shape):
-        return torch.empty(*shape, dtype=torch.float32, device=self.dev)
 
     def gemm(self, tA, tB, M, N, K, A, lda, sA, Bm, ldb, sB, beta, C, ldc, sC, batch=1, bias=None, add=None,
              add_ld=0, add_mod=0, bias_grad=None, alpha=1.0, side=None):
@@ -205,14 +157,7 @@ class _Program:
         self.L.vc_gemm(tA, tB, M, N, K, alpha, A, lda, sA, Bm, ldb, sB, beta, C, ldc, sC, batch, bias, add, add_ld,
                        add_mod, 0, bias_grad, scr, self.SCRATCH, st)
 
-    def ln(self, pfx, X, R, ldx):
-        D = self.m.D
-        Y, mu, rs = self.new(R, D), self.new(R), self.new(R)
-        self.L.vc_layernorm_fwd(R, D, X, ldx, self.P[pfx + ".weight"], self.P[pfx + ".bias"], LN_EPS, Y.data_ptr(), D,
-                                mu.data_ptr(), rs.data_ptr(), self.s)
-        return Y, mu, rs
-
-    def forward(self):
+    def _forward(self):
         return self.layers(self.embed())
 
     def embed(self):
@@ -315,7 +260,7 @@ class _Program:
         writes a buffer the parameter gradients read (the LayerNorm backward writes the residual sum to a new
         buffer: vc_layernorm_bwd_dx with res), and every buffer they read stays referenced until the join.
         Per-launch arithmetic and per-stream order do not depend on the mode: the same bits."""
-        m, L = self.m, self.L
+        L = self.L
         main = torch.cuda.current_stream(self.dev)
         side_stream = self._side_stream() if _SIDE_STREAM in (1, 2) else main
         scr2 = self.new(self.SCRATCH) if side_stream is not main else self.scr
@@ -351,12 +296,9 @@ class _Program:
             if _SIDE_STREAM not in (2, 3):
                 flush()
 
-        grad = self.new(m._n_params)
-        L.vc_fill(m._n_params, grad.data_ptr(), 0.0, self.s)
-        gb = grad.data_ptr()
-        G = {n: gb + F32 * o for n, o in m._poff.items()}
-        dX = self.layers_bwd(dlogits, G, sd, side, flush)
-        self.embed_bwd(dX, G, sd, side)
+        grad = self.new_grad()
+        dX = self.layers_bwd(dlogits, self.G, sd, side, flush)
+        self.embed_bwd(dX, self.G, sd, side)
         flush()
         # join: the gradient is complete when the side stream is; its buffers may go back to the allocator after it
         if side_stream is not main:

@@ -15,7 +15,7 @@ from __future__ import annotations
 import torch
 
 GOLDEN = 0x9E3779B97F4A7C15
-SITE_STRIDE = 1000003        # site k of a forward uses seed + SITE_STRIDE * k (s2eft.py, mft.py, hctnet.py)
+SITE_STRIDE = 1000003        # site k of a forward uses seed + SITE_STRIDE * k (program.py, hctnet.py)
 _M64 = (1 << 64) - 1
 _ATTR = "_vc_seed_state"
 
@@ -36,12 +36,13 @@ def site_offset(k: int) -> int:
     return SITE_STRIDE * k
 
 
-def host_base() -> int:
-    """one draw from torch's CPU generator with the rank mixed in, exactly as the programs seed a forward: the same
-    `torch.manual_seed` reproduces a run, and data-parallel replicas differ"""
+def host_seed() -> int:
+    """one draw from torch's CPU generator with the rank mixed in: a forward's mask seed (program.seed_dropout) or an
+    attached state's base.  The same `torch.manual_seed` reproduces a run; under data parallelism every rank seeds
+    torch alike, so the replicas must differ here -- they must not apply the same keep masks to their shards"""
     from .parallel import rank
-    base = int(torch.randint(0, 2 ** 62, (1,)).item())
-    return (base + GOLDEN * rank()) % (1 << 62)
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    return (seed + GOLDEN * rank()) % (1 << 62)
 
 
 def _i64(v: int) -> int:
@@ -90,7 +91,7 @@ def attach(model, base: int | None = None) -> SeedState:
         raise TypeError("seeds.attach expects one of the package's flat-parameter models")
     if flat.device.type != "cuda":
         raise RuntimeError("seeds.attach: move the model to its ROCm (cuda) device first")
-    st = SeedState(host_base() if base is None else base, flat.device)
+    st = SeedState(host_seed() if base is None else base, flat.device)
     object.__setattr__(model, _ATTR, st)
     return st
 

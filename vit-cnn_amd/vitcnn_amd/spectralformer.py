@@ -23,7 +23,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import s2eft
+from . import program, s2eft
 from .flat import FlatParams
 
 T_MAX = 256   # vc_s2eft_attn_*'s bound on the token count
@@ -71,11 +71,7 @@ class SpectralFormer(FlatParams, nn.Module):
         if x1.shape[0] != x2.shape[0] or x1.shape[1] + x2.shape[1] != self.N:
             raise RuntimeError(f"expected x1 [B, C1] and x2 [B, C2] with C1 + C2 = {self.N}, got {list(x1.shape)} / "
                                f"{list(x2.shape)}")
-        self._ensure_flat()
-        if self._flat_store.device != x1.device:
-            raise RuntimeError("model and inputs are on different devices")
-        needs_grad = torch.is_grad_enabled() and self._flat_store.requires_grad
-        return _SpectralFormerFunction.apply(self, x1, x2, self._flat_store, needs_grad)
+        return program.run(self, _Program, x1, x2)
 
 
 def _pixel_rows(x, name):
@@ -88,28 +84,13 @@ def _pixel_rows(x, name):
     return x.detach().to(torch.float32).contiguous()
 
 
-class _SpectralFormerFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x1, x2, flat, needs_grad):
-        prog = _Program(model, x1, x2)
-        logits = prog.forward()
-        ctx.prog = prog if needs_grad else None
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        if ctx.prog is None:
-            raise RuntimeError("SpectralFormer: backward through a forward run without grad")
-        grad = ctx.prog.backward(dlogits.detach().to(torch.float32).contiguous())
-        ctx.prog = None
-        return None, None, None, grad, None
-
-
 class _Program(s2eft._Program):
     """S2EFT's program with the per-band embedding in place of the gate + patch GEMM"""
 
-    def __init__(self, m, x1, x2):
-        super().__init__(m, x1)
+    NAME = "SpectralFormer"
+
+    def __init__(self, m, needs_grad, x1, x2):
+        super().__init__(m, needs_grad, x1)
         self.x1, self.x2 = x1, x2
         self.C1, self.C2 = x1.shape[1], x2.shape[1]
 

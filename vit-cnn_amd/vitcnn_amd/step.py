@@ -12,6 +12,7 @@ multi-stream step — forward, CE, backward and AdamW — into one hipGraph.
 from __future__ import annotations
 
 import inspect
+from functools import partial
 
 import torch
 
@@ -20,6 +21,7 @@ from .flat import FlatParams, expose_grad_views
 from .losses import Cross_fusion_CNN_Loss, CrossEntropyLoss, EndNet_Loss, ce_forward_backward
 from .model import Multimodality_Mamba, _Program
 from .optim import AdamW
+from .program import counters
 
 
 def fused_train_step(model: Multimodality_Mamba, criterion: CrossEntropyLoss, hsi, lidar, target,
@@ -177,31 +179,8 @@ class TrainStepper:
             self.graphs, self.seen = {}, set()
             self.binding = key
 
-    def _eager_fused(self, data, data2, target):
-        self.opt.zero_grad(set_to_none=True)
+    def _fused_step(self, data, data2, target):
         return fused_train_step(self.net, self.crit, data, data2, target, optimizer=self.opt, exchange=self.exchange)
-
-    def _capture(self, key, data, data2, target):
-        dev = data.device
-        c = _Captured(torch.empty_like(data, memory_format=torch.contiguous_format),
-                      torch.empty_like(data2, memory_format=torch.contiguous_format),
-                      torch.empty(target.shape, dtype=torch.int64, device=dev))
-        torch.cuda.synchronize(dev)
-        self.opt.sync_hyper()          # nothing may change inside the capture (AdamW.step's copy)
-        self.opt.zero_grad(set_to_none=True)
-        try:
-            with torch.cuda.graph(c.graph):
-                c.loss = fused_train_step(self.net, self.crit, c.hsi, c.lidar, c.target, optimizer=self.opt,
-                                          exchange=self.exchange)
-        except RuntimeError as e:    # reported through `launch`, and this shape stays eager
-            torch.cuda.synchronize(dev)
-            self.opt.zero_grad(set_to_none=True)
-            self.launch = f"eager (graph capture failed: {str(e)[:100]})"
-            self.use_graph = False
-            return None
-        c.grad = self.net.flat_params.grad
-        self.graphs[key] = c
-        return c
 
     def _autograd_step(self, st, data, data2, target):
         """the reference sequence on the current stream, the seed advanced first; eager and captured alike"""
@@ -212,22 +191,23 @@ class TrainStepper:
         self.opt.step()
         return loss.detach()
 
-    def _capture_generic(self, key, st, data, data2, target):
+    def _capture(self, key, run, data, data2, target, target_dtype):
+        """`run(hsi, lidar, target)` over static copies of this batch's shapes, captured into a hipGraph"""
         dev = data.device
         c = _Captured(torch.empty_like(data, memory_format=torch.contiguous_format),
                       torch.empty_like(data2, memory_format=torch.contiguous_format),
-                      torch.empty_like(target, memory_format=torch.contiguous_format))
+                      torch.empty(target.shape, dtype=target_dtype, device=dev))
         torch.cuda.synchronize(dev)
-        self.opt.sync_hyper()          # nothing may change inside the capture (the optimizer's copy)
+        self.opt.sync_hyper()          # nothing may change inside the capture (AdamW.step's copy)
         self.opt.zero_grad(set_to_none=True)
         ctx = torch.cuda.graph(c.graph)
-        # the capture stream's arrival counters (cached per stream for the process) are created and zeroed now, not
-        # by a node of this graph: a capture that fails would otherwise leave them cached and never zeroed
-        from .fusatnet import _counters
-        _counters(dev, ctx.capture_stream.cuda_stream)
+        if self.generic:
+            # the capture stream's arrival counters (cached per stream for the process) are created and zeroed now,
+            # not by a node of this graph: a capture that fails would otherwise leave them cached and never zeroed
+            counters(dev, ctx.capture_stream.cuda_stream)
         try:
             with ctx:
-                c.loss = self._autograd_step(st, c.hsi, c.lidar, c.target)
+                c.loss = run(c.hsi, c.lidar, c.target)
         except RuntimeError as e:    # reported through `launch`, and every shape stays eager
             torch.cuda.synchronize(dev)
             self.opt.zero_grad(set_to_none=True)
@@ -238,40 +218,10 @@ class TrainStepper:
         self.graphs[key] = c
         return c
 
-    def _step_generic(self, data, data2, target):
-        net = self.net
-        dev = net.flat_params.device
-        data = data.to(dev, non_blocking=True)
-        data2 = data2.to(dev, non_blocking=True)
-        target = target.to(dev, non_blocking=True)
-        net._ensure_flat()
-        self.opt._device_state(net.flat_params)   # the optimizer state exists before the binding is taken
-        st = seeds.state(net)
-        if st is None and self._drops:
-            st = seeds.attach(net)
-        self._check_binding()
-        key = (tuple(data.shape), data.dtype, tuple(data2.shape), data2.dtype, tuple(target.shape), target.dtype)
-        c = self.graphs.get(key)
-        if c is None and self.use_graph and key in self.seen:
-            c = self._capture_generic(key, st, data, data2, target)
-        self.seen.add(key)
-        if c is None:
-            self.opt.zero_grad(set_to_none=True)
-            return self._autograd_step(st, data, data2, target)
-        c.hsi.copy_(data)
-        c.lidar.copy_(data2)
-        c.target.copy_(target)
-        self.opt.sync_hyper()
-        c.graph.replay()
-        net.flat_params.grad = c.grad
-        return c.loss
-
     def step(self, data, data2, target):
         """one optimizer step on this batch; returns the loss as a device scalar"""
         net = self.net
-        if self.generic:
-            return self._step_generic(data, data2, target)
-        if not self.fused:
+        if not (self.fused or self.generic):
             self.opt.zero_grad()
             out = net(data, data2)
             loss = self.crit(out, target)
@@ -285,14 +235,23 @@ class TrainStepper:
         target = target.to(dev, non_blocking=True)
         net._ensure_flat()
         self.opt._device_state(net.flat_params)   # the optimizer state exists before the binding is taken
+        if self.generic:
+            st = seeds.state(net)
+            if st is None and self._drops:
+                st = seeds.attach(net)
+            run, target_dtype = partial(self._autograd_step, st), target.dtype
+            key = (tuple(data.shape), data.dtype, tuple(data2.shape), data2.dtype, tuple(target.shape), target.dtype)
+        else:
+            run, target_dtype = self._fused_step, torch.int64
+            key = (tuple(data.shape), tuple(data2.shape), tuple(target.shape))
         self._check_binding()
-        key = (tuple(data.shape), tuple(data2.shape), tuple(target.shape))
         c = self.graphs.get(key)
         if c is None and self.use_graph and key in self.seen:
-            c = self._capture(key, data, data2, target)
+            c = self._capture(key, run, data, data2, target, target_dtype)
         self.seen.add(key)
         if c is None:
-            return self._eager_fused(data, data2, target)
+            self.opt.zero_grad(set_to_none=True)
+            return run(data, data2, target)
         c.hsi.copy_(data)
         c.lidar.copy_(data2)
         c.target.copy_(target)
