@@ -240,6 +240,27 @@ VC_API int vc_conv3x3_tap_dgrad(int B, int H, int W, int C, int O, int pad, cons
 VC_API int vc_conv3x3_tap_wgrad_oihw(int B, int H, int W, int C, int O, int pad, const float* x, long ldx,
                                      const float* dy, long lddy, float* dw, float* db, float* ws, long ws_floats,
                                      hipStream_t stream);
+/* The four tap-major convs with `flags` (the plain entry points are these with flags 0, bit-identical).
+ * VC_CONV_BF16 (bit value 2, as vc_gemm's flags & 2): both operands of the contraction are rounded RNE to bf16
+ * as the MFMA fragments are formed -- x and Wt (fwd), dy and x (wgrad), dy and Wt (dgrad) -- and the products are
+ * accumulated in fp32 (v_mfma_f32_16x16x32_bf16 over the same fp32 LDS stages on the pipelined route; rounded
+ * operands on the fp32 MFMAs of the register-staged route: products of bf16 values are exact in fp32, so the two
+ * routes compute the same sums).  The bias add, beta dx, the fused bias gradient db = colsum(dy) (unrounded dy),
+ * the split-K slabs and their fixed-order combine stay fp32; zero padding stays zero; the split plans are those of
+ * flags 0, so a result is run-to-run bit-identical.  Any other flag bit is refused. */
+#define VC_CONV_BF16 2
+VC_API int vc_conv3x3_tap_fwd_ex(int B, int H, int W, int C, int O, int pad, const float* x, long ldx,
+                                 const float* wt, const float* bias, float* y, long ldy, float* ws, long ws_floats,
+                                 int flags, hipStream_t stream);
+VC_API int vc_conv3x3_tap_wgrad_ex(int B, int H, int W, int C, int O, int pad, const float* x, long ldx,
+                                   const float* dy, long lddy, float* dwt, float* ws, long ws_floats, int flags,
+                                   hipStream_t stream);
+VC_API int vc_conv3x3_tap_wgrad_oihw_ex(int B, int H, int W, int C, int O, int pad, const float* x, long ldx,
+                                        const float* dy, long lddy, float* dw, float* db, float* ws, long ws_floats,
+                                        int flags, hipStream_t stream);
+VC_API int vc_conv3x3_tap_dgrad_ex(int B, int H, int W, int C, int O, int pad, const float* dy, long lddy,
+                                   const float* wt, float beta, float* dx, long lddx, float* ws, long ws_floats,
+                                   int flags, hipStream_t stream);
 /* train-mode BatchNorm(x) (statistics as vc_bn_stats_ex: save_* and running stats written) followed by
  * vc_im2col3x3 of the normalised x, the statistics' final reduction done inside the im2col launch
  * (ms_conv_bn_relu's BN -> conv3x3, Mutimodality_Mamba7.py:1035-1048); bit-identical to the two calls. */

@@ -1,5 +1,13 @@
 """GPU tool: bench.py's config-5 leg alone -- the FusAtNet B=64 training step as one hipGraph (and its
-train-mode forward); prints the leg's JSON.  usage: python tools/fusat_step.py [steps]"""
+train-mode forward); prints the leg's JSON.
+usage: python tools/fusat_step.py [steps] [--precision {fp32,bf16}]
+
+--precision bf16 runs the same leg on a model built with precision="bf16": bench.py's leg
+builds `FusAtNet(144, 1, 16)`, so the tool hands it a class whose default precision is bf16 for the call.  The line
+is the same; "dtype" names the mode, and since "mfma_frac" stays relative to the fp32 MFMA peak, as in the fp32 line,
+the bf16 line says so in "mfma_frac_of".  (The class is looked up on `vitcnn_amd.fusatnet` when the leg runs; if
+bench.py ever binds it earlier, the check below fails loudly instead of timing an fp32 model.)"""
+import argparse
 import json
 import os
 import sys
@@ -14,10 +22,38 @@ import knobs  # noqa: F401,E402  (measurement switches: tools/knobs.py)
 import bench  # noqa: E402
 
 
+def fusat_leg(steps, precision):
+    from vitcnn_amd import fusatnet
+    if precision == "fp32":
+        return bench.fusat_leg(torch.device("cuda", 0), steps, False)[0]
+    orig = fusatnet.FusAtNet
+
+    built = []
+
+    class FusAtNetBf16(orig):
+        def __init__(self, *args, **kwargs):
+            kwargs.setdefault("precision", precision)
+            super().__init__(*args, **kwargs)
+            built.append(self.precision)
+
+    fusatnet.FusAtNet = FusAtNetBf16
+    try:
+        out = bench.fusat_leg(torch.device("cuda", 0), steps, False)[0]
+    finally:
+        fusatnet.FusAtNet = orig
+    if built != [precision]:
+        raise RuntimeError(f"the leg did not build one {precision} model (built: {built})")
+    out["dtype"] = "bf16 3x3-conv operands, fp32 accumulation"
+    out["mfma_frac_of"] = "fp32 MFMA peak"
+    return out
+
+
 def main():
-    steps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-    out, _ = bench.fusat_leg(torch.device("cuda", 0), steps, False)
-    print(json.dumps(out), flush=True)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("steps", nargs="?", type=int, default=5)
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
+    a = ap.parse_args()
+    print(json.dumps(fusat_leg(a.steps, a.precision)), flush=True)
 
 
 if __name__ == "__main__":

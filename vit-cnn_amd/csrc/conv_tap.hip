@@ -104,7 +104,14 @@ __device__ __forceinline__ void load4(const float* base, long ld, int row, int c
   }
 }
 
-template <int MODE>
+// an fp32 value rounded RNE to bf16, as fp32 (v_cvt_pk_bf16_f32: the rounding of g2::pk_bf16)
+__device__ __forceinline__ float rne_bf16(float v) { return __uint_as_float(g2::pk_bf16(v, 0.f) << 16); }
+
+// BF (VC_CONV_BF16): both operands rounded RNE to bf16 once, as they are staged into the LDS images -- except the
+// weight gradient's A image (dy^T), which stays fp32 because the bias column sums the unrounded dy from it and is
+// rounded as its fragments are read instead; products of bf16 values are exact in fp32, so the fp32 MFMAs below
+// accumulate what conv_pipe's bf16 MFMAs accumulate
+template <int MODE, bool BF = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void conv_tap(TapArgs a) {
   constexpr int PA = MODE == WGRAD ? PO : PK;   // A: dy^T (k-outer) for wgrad, row gathers (k-contiguous) else
   constexpr int PB = MODE == FWD ? PK : PO;     // B: Wt rows (k-contiguous) for fwd, k-outer else
@@ -178,6 +185,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
     }
   };
   auto store = [&]() {
+    if constexpr (BF) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        if (MODE != WGRAD) ra[e] = rne_bf16(ra[e]);
+        rbv[e] = rne_bf16(rbv[e]);
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if constexpr (MODE == WGRAD) {
@@ -223,10 +237,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
 #pragma unroll
       for (int ks = 0; ks < TK / 2; ++ks) {
         const int k = 2 * ks + h;
-        const float a0 = As[k * PA + wm * 64 + l31];
-        const float a1 = As[k * PA + wm * 64 + 32 + l31];
-        const float b0 = Bs[k * PB + wn * 64 + l31];
-        const float b1 = Bs[k * PB + wn * 64 + 32 + l31];
+        float a0 = As[k * PA + wm * 64 + l31];
+        float a1 = As[k * PA + wm * 64 + 32 + l31];
+        float b0 = Bs[k * PB + wn * 64 + l31];
+        float b1 = Bs[k * PB + wn * 64 + 32 + l31];
+        if constexpr (BF && MODE == WGRAD) {   // the A image holds the unrounded dy (bias column above)
+          a0 = rne_bf16(a0); a1 = rne_bf16(a1);
+        }
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
         acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
         acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
@@ -404,8 +421,13 @@ __global__ __launch_bounds__(256) void conv_pack_many(PackMany P) {
 constexpr int CP_B = 64;   // output tile (both sides)
 
 // NW = 8 (round 5): the tile on 2 x 4 waves of 32 x 16 (two waves per SIMD, one DMA piece per operand per wave),
-// as gemm.hip's pipelined kernel
-template <int MODE, int NW = 4>
+// as gemm.hip's pipelined kernel.
+// BF (VC_CONV_BF16): the same fp32 stages and DMA ring; the k-tile's fragments are rounded RNE to bf16 as they are
+// formed and multiplied by one v_mfma_f32_16x16x32_bf16 per output tile (gp::mma_ktile_bf: the fp32 fragment reads of
+// the K-contiguous and the row-contiguous image both hand element j of lane group g the k 16 s + 4 g + j, so A and B
+// pair the same k in either image).  Accumulators, the bias add, beta dx, the bias-gradient column (summed from the
+// fp32 stage) and the split-K slabs stay fp32; the DMA's zero fill stays zero.
+template <int MODE, int NW = 4, bool BF = false>
 __global__ __launch_bounds__(64 * NW) void conv_pipe(TapArgs a, int tn, int nsplit, unsigned total) {
   constexpr int BM = CP_B, BN = CP_B, WN = NW / 2, NS = 2, QN = 8 / NW;
   constexpr int WTM = BM / 2, WTN = BN / WN, MT = WTM / 16, NT = WTN / 16;
@@ -514,7 +536,8 @@ __global__ __launch_bounds__(64 * NW) void conv_pipe(TapArgs a, int tn, int nspl
       for (int k = 0; k < 32 / NW; ++k)
         bacc += *reinterpret_cast<const float*>(cur + SA::rc_off((32 / NW) * kq + k, mm));
     }
-    g2::mma_ktile<false, MT, NT, SA, SB, 1>(cur, cur + SA_B, wm * WTM, wn * WTN, lane, acc);
+    if constexpr (BF) gp::mma_ktile_bf<MT, NT, SA, SB>(cur, cur + SA_B, wm * WTM, wn * WTN, lane, acc[0]);
+    else g2::mma_ktile<false, MT, NT, SA, SB, 1>(cur, cur + SA_B, wm * WTM, wn * WTN, lane, acc);
   }
   (void)LOADS;
   const bool split = nsplit > 1;
@@ -560,7 +583,7 @@ __global__ __launch_bounds__(64 * NW) void conv_pipe(TapArgs a, int tn, int nspl
 bool vec_ok(const float* p, long ld) { return p && ((uintptr_t)p % 16 == 0) && (ld % 4 == 0); }
 
 template <int MODE>
-int launch_tap(TapArgs& a, int grid_n, int grid_m, float* ws, long ws_floats, hipStream_t stream) {
+int launch_tap(TapArgs& a, int grid_n, int grid_m, float* ws, long ws_floats, bool bf, hipStream_t stream) {
   // split K so the grid fills one round of resident blocks (256 CUs x 3 blocks: 164 VGPRs, 34 KB LDS)
   // without a ragged second round; slices of >= 4 k-tiles; the slabs must fit the workspace
   const long tiles = (long)grid_n * grid_m;
@@ -575,7 +598,8 @@ int launch_tap(TapArgs& a, int grid_n, int grid_m, float* ws, long ws_floats, hi
   nsplit = vc_cdiv(a.nk, a.kper);
   a.part = nsplit > 1 ? ws : nullptr;
   VC_REQUIRE(grid_m < 65536 && nsplit < 65536);
-  hipLaunchKernelGGL(conv_tap<MODE>, dim3(grid_n, grid_m, nsplit), dim3(256), 0, stream, a);
+  if (bf) hipLaunchKernelGGL((conv_tap<MODE, true>), dim3(grid_n, grid_m, nsplit), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((conv_tap<MODE, false>), dim3(grid_n, grid_m, nsplit), dim3(256), 0, stream, a);
   VC_CHECK_LAUNCH();
   if (nsplit > 1) {
     const long n = (long)a.M * a.N;
@@ -590,7 +614,7 @@ int launch_tap(TapArgs& a, int grid_n, int grid_m, float* ws, long ws_floats, hi
 // the pipelined kernel's launch: split K (slices of >= 4 k-tiles, towards ~512 blocks) only for grids
 // of < 128 tiles -- the plan of gemm.hip's plan_pipe; the same split-K combine as conv_tap
 template <int MODE>
-int launch_conv_pipe(TapArgs& a, int grid_n, float* ws, long ws_floats, hipStream_t stream) {
+int launch_conv_pipe(TapArgs& a, int grid_n, float* ws, long ws_floats, bool bf, hipStream_t stream) {
   const int tm = vc_cdiv(a.M, CP_B);
   const long tiles = (long)grid_n * tm;
   int nsplit = 1;
@@ -607,8 +631,15 @@ int launch_conv_pipe(TapArgs& a, int grid_n, float* ws, long ws_floats, hipStrea
   a.part = nsplit > 1 ? ws : nullptr;
   const long total = tiles * nsplit;
   VC_REQUIRE(total < (1L << 31));
-  if (vc_knob("VITCNN_CONV_PIPE_W8", 1))   // 8 waves (knob: probe library)
+  const bool w8 = vc_knob("VITCNN_CONV_PIPE_W8", 1);   // 8 waves (knob: probe library)
+  if (w8 && bf)
+    hipLaunchKernelGGL((conv_pipe<MODE, 8, true>), dim3((unsigned)total), dim3(512), 0, stream, a, grid_n, nsplit,
+                       (unsigned)total);
+  else if (w8)
     hipLaunchKernelGGL((conv_pipe<MODE, 8>), dim3((unsigned)total), dim3(512), 0, stream, a, grid_n, nsplit,
+                       (unsigned)total);
+  else if (bf)
+    hipLaunchKernelGGL((conv_pipe<MODE, 4, true>), dim3((unsigned)total), dim3(256), 0, stream, a, grid_n, nsplit,
                        (unsigned)total);
   else
     hipLaunchKernelGGL((conv_pipe<MODE, 4>), dim3((unsigned)total), dim3(256), 0, stream, a, grid_n, nsplit,
@@ -686,8 +717,11 @@ VC_EXPORT int vc_conv3x3_pack_many(int n, const int* shapes, const float* const*
   return VC_OK;
 }
 
-VC_EXPORT int vc_conv3x3_tap_fwd(int B, int H, int W, int C, int O, int pad, const float* x, long ldx, const float* wt,
-                                 const float* bias, float* y, long ldy, float* ws, long ws_floats, hipStream_t stream) {
+VC_EXPORT int vc_conv3x3_tap_fwd_ex(int B, int H, int W, int C, int O, int pad, const float* x, long ldx,
+                                    const float* wt, const float* bias, float* y, long ldy, float* ws, long ws_floats,
+                                    int flags, hipStream_t stream) {
+  VC_REQUIRE((flags & ~VC_CONV_BF16) == 0);
+  const bool bf = flags & VC_CONV_BF16;
   VC_REQUIRE(B > 0 && H >= 3 - 2 * pad && W >= 3 - 2 * pad && C > 0 && O > 0 && (pad == 0 || pad == 1));
   VC_REQUIRE(x && wt && y && ldx >= C && ldy >= O);
   TapArgs a = geo(B, H, W, C, O, pad);
@@ -699,12 +733,19 @@ VC_EXPORT int vc_conv3x3_tap_fwd(int B, int H, int W, int C, int O, int pad, con
   a.nk = 9 * a.tpt;
   a.x = x; a.ldx = ldx; a.w = wt; a.bias = bias; a.out = y; a.ldo = ldy;
   a.vx = vec_ok(x, ldx); a.vw = vec_ok(wt, a.Cw);
-  if (conv_pipe_ok(FWD, a, x, ldx, wt, 4)) return launch_conv_pipe<FWD>(a, vc_cdiv(O, CP_B), ws, ws_floats, stream);
-  return launch_tap<FWD>(a, vc_cdiv(O, TN), vc_cdiv(a.M, TM), ws, ws_floats, stream);
+  if (conv_pipe_ok(FWD, a, x, ldx, wt, 4)) return launch_conv_pipe<FWD>(a, vc_cdiv(O, CP_B), ws, ws_floats, bf, stream);
+  return launch_tap<FWD>(a, vc_cdiv(O, TN), vc_cdiv(a.M, TM), ws, ws_floats, bf, stream);
+}
+
+VC_EXPORT int vc_conv3x3_tap_fwd(int B, int H, int W, int C, int O, int pad, const float* x, long ldx, const float* wt,
+                                 const float* bias, float* y, long ldy, float* ws, long ws_floats, hipStream_t stream) {
+  return vc_conv3x3_tap_fwd_ex(B, H, W, C, O, pad, x, ldx, wt, bias, y, ldy, ws, ws_floats, 0, stream);
 }
 
 static int tap_wgrad(int B, int H, int W, int C, int O, int pad, const float* x, long ldx, const float* dy, long lddy,
-                     float* dwt, int oihw, float* db, float* ws, long ws_floats, hipStream_t stream) {
+                     float* dwt, int oihw, float* db, float* ws, long ws_floats, int flags, hipStream_t stream) {
+  VC_REQUIRE((flags & ~VC_CONV_BF16) == 0);
+  const bool bf = flags & VC_CONV_BF16;
   VC_REQUIRE(B > 0 && H >= 3 - 2 * pad && W >= 3 - 2 * pad && C > 0 && O > 0 && (pad == 0 || pad == 1));
   VC_REQUIRE(x && dy && dwt && ldx >= C && lddy >= O);
   TapArgs a = geo(B, H, W, C, O, pad);
@@ -722,26 +763,40 @@ static int tap_wgrad(int B, int H, int W, int C, int O, int pad, const float* x,
   a.vx = vec_ok(x, ldx); a.vdy = vec_ok(dy, lddy);
   if (conv_pipe_ok(WGRAD, a, x, ldx, dy, lddy)) {
     a.tpt = vc_cdiv(C, CP_B);   // n-tiles per tap
-    return launch_conv_pipe<WGRAD>(a, 9 * a.tpt, ws, ws_floats, stream);
+    return launch_conv_pipe<WGRAD>(a, 9 * a.tpt, ws, ws_floats, bf, stream);
   }
-  return launch_tap<WGRAD>(a, 9 * a.tpt, vc_cdiv(O, TM), ws, ws_floats, stream);
+  return launch_tap<WGRAD>(a, 9 * a.tpt, vc_cdiv(O, TM), ws, ws_floats, bf, stream);
 }
 
 VC_EXPORT int vc_conv3x3_tap_wgrad(int B, int H, int W, int C, int O, int pad, const float* x, long ldx,
                                    const float* dy, long lddy, float* dwt, float* ws, long ws_floats,
                                    hipStream_t stream) {
-  return tap_wgrad(B, H, W, C, O, pad, x, ldx, dy, lddy, dwt, 0, nullptr, ws, ws_floats, stream);
+  return tap_wgrad(B, H, W, C, O, pad, x, ldx, dy, lddy, dwt, 0, nullptr, ws, ws_floats, 0, stream);
+}
+
+VC_EXPORT int vc_conv3x3_tap_wgrad_ex(int B, int H, int W, int C, int O, int pad, const float* x, long ldx,
+                                      const float* dy, long lddy, float* dwt, float* ws, long ws_floats, int flags,
+                                      hipStream_t stream) {
+  return tap_wgrad(B, H, W, C, O, pad, x, ldx, dy, lddy, dwt, 0, nullptr, ws, ws_floats, flags, stream);
 }
 
 VC_EXPORT int vc_conv3x3_tap_wgrad_oihw(int B, int H, int W, int C, int O, int pad, const float* x, long ldx,
                                         const float* dy, long lddy, float* dw, float* db, float* ws, long ws_floats,
                                         hipStream_t stream) {
-  return tap_wgrad(B, H, W, C, O, pad, x, ldx, dy, lddy, dw, 1, db, ws, ws_floats, stream);
+  return tap_wgrad(B, H, W, C, O, pad, x, ldx, dy, lddy, dw, 1, db, ws, ws_floats, 0, stream);
 }
 
-VC_EXPORT int vc_conv3x3_tap_dgrad(int B, int H, int W, int C, int O, int pad, const float* dy, long lddy,
-                                   const float* wt, float beta, float* dx, long lddx, float* ws, long ws_floats,
-                                   hipStream_t stream) {
+VC_EXPORT int vc_conv3x3_tap_wgrad_oihw_ex(int B, int H, int W, int C, int O, int pad, const float* x, long ldx,
+                                           const float* dy, long lddy, float* dw, float* db, float* ws, long ws_floats,
+                                           int flags, hipStream_t stream) {
+  return tap_wgrad(B, H, W, C, O, pad, x, ldx, dy, lddy, dw, 1, db, ws, ws_floats, flags, stream);
+}
+
+VC_EXPORT int vc_conv3x3_tap_dgrad_ex(int B, int H, int W, int C, int O, int pad, const float* dy, long lddy,
+                                      const float* wt, float beta, float* dx, long lddx, float* ws, long ws_floats,
+                                      int flags, hipStream_t stream) {
+  VC_REQUIRE((flags & ~VC_CONV_BF16) == 0);
+  const bool bf = flags & VC_CONV_BF16;
   VC_REQUIRE(B > 0 && H >= 3 - 2 * pad && W >= 3 - 2 * pad && C > 0 && O > 0 && (pad == 0 || pad == 1));
   VC_REQUIRE(dy && wt && dx && lddy >= O && lddx >= C);
   TapArgs a = geo(B, H, W, C, O, pad);
@@ -753,6 +808,13 @@ VC_EXPORT int vc_conv3x3_tap_dgrad(int B, int H, int W, int C, int O, int pad, c
   a.nk = 9 * a.tpt;
   a.dy = dy; a.lddy = lddy; a.w = wt; a.out = dx; a.ldo = lddx; a.beta = beta;
   a.vdy = vec_ok(dy, lddy); a.vw = vec_ok(wt, a.Cw);
-  if (conv_pipe_ok(DGRAD, a, dy, lddy, wt, 4)) return launch_conv_pipe<DGRAD>(a, vc_cdiv(C, CP_B), ws, ws_floats, stream);
-  return launch_tap<DGRAD>(a, vc_cdiv(C, TN), vc_cdiv(a.M, TM), ws, ws_floats, stream);
+  if (conv_pipe_ok(DGRAD, a, dy, lddy, wt, 4))
+    return launch_conv_pipe<DGRAD>(a, vc_cdiv(C, CP_B), ws, ws_floats, bf, stream);
+  return launch_tap<DGRAD>(a, vc_cdiv(C, TN), vc_cdiv(a.M, TM), ws, ws_floats, bf, stream);
+}
+
+VC_EXPORT int vc_conv3x3_tap_dgrad(int B, int H, int W, int C, int O, int pad, const float* dy, long lddy,
+                                   const float* wt, float beta, float* dx, long lddx, float* ws, long ws_floats,
+                                   hipStream_t stream) {
+  return vc_conv3x3_tap_dgrad_ex(B, H, W, C, O, pad, dy, lddy, wt, beta, dx, lddx, ws, ws_floats, 0, stream);
 }

@@ -653,37 +653,7 @@ __global__ __launch_bounds__(256) void splitk_reduce4(GemmArgs g, long nelem, in
 // per output tile; MT * NT >= 4 independent chains keep the 32-cycle issue rate.
 namespace gp {
 
-// bf16 operands (config 2) over the same fp32 stage: a lane's two fp32 fragments of the k-tile (sub-steps
-// 0 and 1, k = 4g + j and 16 + 4g + j) rounded RNE to bf16 (v_cvt_pk_bf16_f32, g2's staging rounding) and
-// fed to ONE v_mfma_f32_16x16x32_bf16 per output tile -- the MFMA's k order is a permutation applied to
-// both operands alike, so the products are the k-tile's.  Same LDS reads as the fp32 path, 1/8 of the MFMAs.
-template <int MT, int NT, class SA, class SB>
-__device__ __forceinline__ void mma_ktile_bf(const char* As, const char* Bs, int arow, int brow, int lane,
-                                             f32x4 (&acc)[MT][NT]) {
-  uint4 a[MT], b[NT];
-#pragma unroll
-  for (int mi = 0; mi < MT; ++mi) {
-    const uint4 f0 = SA::frag(As, arow + 16 * mi, 0, lane), f1 = SA::frag(As, arow + 16 * mi, 1, lane);
-    a[mi] = uint4{g2::pk_bf16(__uint_as_float(f0.x), __uint_as_float(f0.y)),
-                  g2::pk_bf16(__uint_as_float(f0.z), __uint_as_float(f0.w)),
-                  g2::pk_bf16(__uint_as_float(f1.x), __uint_as_float(f1.y)),
-                  g2::pk_bf16(__uint_as_float(f1.z), __uint_as_float(f1.w))};
-  }
-#pragma unroll
-  for (int ni = 0; ni < NT; ++ni) {
-    const uint4 f0 = SB::frag(Bs, brow + 16 * ni, 0, lane), f1 = SB::frag(Bs, brow + 16 * ni, 1, lane);
-    b[ni] = uint4{g2::pk_bf16(__uint_as_float(f0.x), __uint_as_float(f0.y)),
-                  g2::pk_bf16(__uint_as_float(f0.z), __uint_as_float(f0.w)),
-                  g2::pk_bf16(__uint_as_float(f1.x), __uint_as_float(f1.y)),
-                  g2::pk_bf16(__uint_as_float(f1.z), __uint_as_float(f1.w))};
-  }
-#pragma unroll
-  for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni)
-      acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(g2::bf16x8, a[mi]),
-                                                            __builtin_bit_cast(g2::bf16x8, b[ni]), acc[mi][ni], 0, 0, 0);
-}
+// (mma_ktile_bf, the bf16-operand k-tile step over the fp32 stage, lives in mfma_tiles.h: conv_tap.hip shares it)
 
 // The block's output tile: (xn, ym) of K slice zs / batch zb, tn x tm tiles per slice (the arrival
 // counter's index of the in-launch combine, g.cnt; null = slabs for a separate reduce).  `smem` is the

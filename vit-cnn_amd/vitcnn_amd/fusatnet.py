@@ -21,6 +21,11 @@ weights; `vc_bn_bwd_relu_ex`, the ReLU decisions recomputed from the BN input an
 pooled-scale and product backwards; every gradient buffer written by its first writer with beta 0 instead
 of zero-filled); the parameter gradients land in one flat gradient
 (`flat_params.grad`) for the fused Adam (vitcnn_amd.optim.AdamW, weight_decay 0).
+
+Precision: `FusAtNet(..., precision="bf16")` / `set_precision("bf16")` runs every 3x3 conv's
+three contractions with both operands rounded RNE to bf16 and fp32 accumulation (`vc_conv3x3_tap_*_ex` with
+`VC_CONV_BF16`); master weights, the bias adds and bias gradients, BatchNorm, Adam and all elementwise work stay fp32,
+and so does `cm.conv6`, the 1x1 head (a plain GEMM, < 0.1 % of the step).  "fp32", the default, is the parity mode.
 """
 from __future__ import annotations
 
@@ -32,7 +37,7 @@ import torch.nn as nn
 from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
-from .model import _IMPLICIT_CONV, N_COUNTERS
+from .model import _IMPLICIT_CONV, N_COUNTERS, _check_precision
 
 # 3x3 convs: the tap-major implicit GEMM (vc_conv3x3_tap_*, conv_tap.hip); False restores the im2col +
 # vc_gemm formulation of rounds 1-2 (a module constant: tools/knobs.py sets it from VITCNN_FUSAT_IM2COL=1)
@@ -42,6 +47,7 @@ _TAP_CONV = True
 _PAD_LIDAR = True
 
 BN_EPS = 1e-5
+CONV_BF16 = 2   # VC_CONV_BF16 (include/vitcnn.h): bf16 operands, fp32 accumulation
 _counters = program.counters   # the pool's old name and home, kept importable
 
 
@@ -148,10 +154,15 @@ class FusAtNet(FlatParams, nn.Module):
     """Same constructor as the reference (FusAtNet.py:168-176); forward(x1 [B,C1,P,P], x2 [B,C2,P,P]).
     Parameters live in one flat buffer (vitcnn_amd.flat): the backward writes one flat gradient, which
     the fused optimizer (vitcnn_amd.optim.AdamW with weight_decay=0: the reference's Adam,
-    model_utils.py:109-118) updates in one pass."""
+    model_utils.py:109-118) updates in one pass.
 
-    def __init__(self, input_channels, input_channels2, num_classes):
+    `precision` (keyword only; the positional signature and the state_dict are the reference's): "fp32", the parity
+    mode, or "bf16": the operands of every 3x3 conv contraction (forward, weight and data gradient) rounded to bf16,
+    fp32 accumulation; `cm.conv6`, the 1x1 head, stays an fp32 GEMM."""
+
+    def __init__(self, input_channels, input_channels2, num_classes, *, precision="fp32"):
         super().__init__()
+        self.precision = _check_precision(precision)
         self.hfe = Hyper_Feature_Extractor(input_channels, 1024)
         self.spectral_am = Spectral_Attention_Module(input_channels, 1024)
         self.spatial_am = Spatial_Attention_module(input_channels2, 1024)
@@ -160,6 +171,14 @@ class FusAtNet(FlatParams, nn.Module):
         self.cm = Classification_Module(1024, num_classes)
         self.c1, self.c2, self.ncls = input_channels, input_channels2, num_classes
         self._build_flat()
+
+    def set_precision(self, precision: str):
+        """Arithmetic of the 3x3 convs: "fp32" (the parity mode) or "bf16" (bf16 operands, fp32 accumulation; master
+        weights, BatchNorm, Adam, the 1x1 head and all elementwise work stay fp32).  Every forward builds its program
+        from the current value; a TrainStepper's captured graphs are bound to the precision they recorded and are
+        dropped when it changes."""
+        self.precision = _check_precision(precision)
+        return self
 
     def forward(self, x1: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
         if x1.device.type != "cuda":
@@ -189,6 +208,10 @@ class _Program(program.Program):
         super().__init__(lib(), m, grad, x1, x2)
         self.Pp = x1.shape[2]
         self.x1, self.x2 = x1, x2
+        self.conv_flags = CONV_BF16 if m.precision == "bf16" else 0
+        if self.conv_flags and not _TAP_CONV:
+            raise RuntimeError("FusAtNet precision='bf16' needs the tap-major convs: the im2col / implicit-GEMM "
+                               "measurement routes are fp32 only")
         self.scratch(max(1 << 22, self.B * self.SCRATCH_PER_SAMPLE))
         self.grad = grad
         self.tape = []        # backward closures, run in reverse
@@ -253,11 +276,12 @@ class _Program(program.Program):
         col2im pass exists; the weights are repacked tap-major per step (vc_conv3x3_pack, in the
         captured graph) and the tap-major weight gradient unpacked into the flat gradient.
         VITCNN_FUSAT_IM2COL=1: vc_im2col3x3_pad + vc_gemm (rounds 1-2); VITCNN_IMPLICIT_CONV=1 with it:
-        the element-gather implicit GEMM vc_conv3x3_*."""
+        the element-gather implicit GEMM vc_conv3x3_*.  The model's precision reaches the tap-major route only
+        (`self.conv_flags`, all three directions); the two measurement routes refuse bf16 at program build."""
         B, O = self.B, conv.out_channels
         OH = H + 2 * pad - 2
         M, K = B * OH * OH, C * 9
-        L, scr = self.L, self.scr.data_ptr()
+        L, scr, flags = self.L, self.scr.data_ptr(), self.conv_flags
         y = self.new(B, OH, OH, O)
         wt = None
         if _TAP_CONV:
@@ -265,8 +289,8 @@ class _Program(program.Program):
             if wt is None:
                 wt = self.new(O * 9 * ((C + 3) // 4 * 4))
                 L.vc_conv3x3_pack(O, C, 0, conv.weight.data_ptr(), wt.data_ptr(), 0.0, self.s)
-            L.vc_conv3x3_tap_fwd(B, H, H, C, O, pad, x.data_ptr(), ldx, wt.data_ptr(), conv.bias.data_ptr(),
-                                 y.data_ptr(), O, scr, self.SCRATCH, self.s)
+            L.vc_conv3x3_tap_fwd_ex(B, H, H, C, O, pad, x.data_ptr(), ldx, wt.data_ptr(), conv.bias.data_ptr(),
+                                    y.data_ptr(), O, scr, self.SCRATCH, flags, self.s)
         elif _IMPLICIT_CONV:
             L.vc_conv3x3_fwd(B, H, H, C, O, pad, x.data_ptr(), ldx, None, None, None, None, conv.weight.data_ptr(),
                              conv.bias.data_ptr(), 0, y.data_ptr(), O, scr, self.SCRATCH, self.s)
@@ -280,12 +304,13 @@ class _Program(program.Program):
         def bwd():
             dy = self.grad_of(y)
             if _TAP_CONV:   # weight gradient in the torch layout and the bias gradient, by the wgrad launch
-                L.vc_conv3x3_tap_wgrad_oihw(B, H, H, C, O, pad, x.data_ptr(), ldx, dy.data_ptr(), O,
-                                            self.pgrad(conv.weight), self.pgrad(conv.bias), scr, self.SCRATCH, self.s)
+                L.vc_conv3x3_tap_wgrad_oihw_ex(B, H, H, C, O, pad, x.data_ptr(), ldx, dy.data_ptr(), O,
+                                               self.pgrad(conv.weight), self.pgrad(conv.bias), scr, self.SCRATCH,
+                                               flags, self.s)
                 if id(x) not in self.no_grad_ids:   # every row's C columns written (ldx padding never read)
                     gx, beta = self.acc(x)
-                    L.vc_conv3x3_tap_dgrad(B, H, H, C, O, pad, dy.data_ptr(), O, wt.data_ptr(), beta, gx.data_ptr(),
-                                           ldx, scr, self.SCRATCH, self.s)
+                    L.vc_conv3x3_tap_dgrad_ex(B, H, H, C, O, pad, dy.data_ptr(), O, wt.data_ptr(), beta,
+                                              gx.data_ptr(), ldx, scr, self.SCRATCH, flags, self.s)
                 return
             if _IMPLICIT_CONV:
                 L.vc_conv3x3_wgrad(B, H, H, C, O, pad, x.data_ptr(), ldx, None, None, None, None, dy.data_ptr(), O,

@@ -45,7 +45,8 @@ _EDITS = [
      "sys.stdout = open(filename, 'w')"),
     ("args = parser.parse_args()",
      "parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16'],\n"
-     "                    help='GEMM operand precision of the MI355X ViT-CNN path (bf16: bf16 operands, fp32 accumulation)')\n"
+     "                    help='operand precision of the MI355X path: ViT-CNN GEMMs and FusAtNet 3x3 convs '\n"
+     "                         '(bf16: bf16 operands, fp32 accumulation); other models are fp32 only')\n"
      "args = parser.parse_args()\n"
      "_VC_RANK, _VC_WORLD, _VC_LOCAL = _vc_parallel.init_from_env()"),
     ("CUDA_DEVICE = get_device(args.cuda)",

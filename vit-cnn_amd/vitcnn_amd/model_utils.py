@@ -26,8 +26,9 @@ each rank iterates its own shard of the batches (a loader that is not already sh
 `parallel.ShardedLoader`, which shards a torch DataLoader at its sampler).
 
 Precision (BASELINE.json config 2): `get_model(..., precision="bf16")` builds ViT-CNN with bf16
-GEMM operands and fp32 accumulation (`Multimodality_Mamba.set_precision`); the default "fp32" is
-the parity mode.
+GEMM operands and fp32 accumulation (`Multimodality_Mamba.set_precision`), and FusAtNet with bf16 operands on
+its 3x3 convolutions (`FusAtNet.set_precision`); the default "fp32" is the parity mode.
+The other models have no bf16 mode.
 """
 from __future__ import annotations
 
@@ -139,10 +140,12 @@ def _get_fusatnet(n_bands, n_bands2, n_classes, device, kwargs):
     Adam(lr 1e-3) as in the reference -- the fused AdamW kernel with weight_decay 0 over the model's flat
     parameter buffer (torch.optim.Adam's update exactly) --, weighted CE, epoch 150, batch 64, applyPCA False.
     The reference's backward raises (in-place residual add); this path trains with
-    out-of-place residual semantics (vitcnn_amd/fusatnet.py)."""
+    out-of-place residual semantics (vitcnn_amd/fusatnet.py).  `precision="bf16"`: bf16 operands on the 3x3 convs
+    (`FusAtNet.set_precision`)."""
     from .fusatnet import FusAtNet
     kwargs.setdefault("patch_size", 11)
-    model = FusAtNet(n_bands, n_bands2, n_classes).to(device)
+    precision = kwargs.setdefault("precision", "fp32")
+    model = FusAtNet(n_bands, n_bands2, n_classes, precision=precision).to(device)
     lr = kwargs.setdefault("lr", 0.001)
     optimizer = AdamW(model.parameters(), lr=lr, weight_decay=0.0)
     criterion = CrossEntropyLoss(weight=kwargs["weights"])
