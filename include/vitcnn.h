@@ -547,6 +547,15 @@ VC_API int vc_confusion_matrix(long n, const long long* target, const long long*
  * vc_s2eft_gate_fwd: spectral gate :134-143 (x [B,N,C]; w = conv1d weight [1,2,7] (mean, max),
  *   bias [1]): mask[b,t] = sigmoid(conv1d_k7_pad3([mean_c x, max_c x]))[t] >= beta; xg = x * mask
  *   (the reference thresholds `.data`: no gradient reaches the gate).
+ * vc_s2eft_patch_gate_fwd: the same gate straight from the two NCHW patches x1 [B,C1,P,P], x2 [B,C2,P,P]
+ *   (x2 may be null when C2 = 0), over the circular neighbour-band token rows, which are never stored:
+ *   with r = cat(x1, x2) over channels viewed [B, N = C1 + C2, P*P] and near in {1, 3},
+ *   tokens[b, j, s*P*P + p] = r[b, (j + s - near/2) mod N, p]  (row j = previous, this, next band; the LiDAR
+ *   band neighbours the last HSI band and HSI band 0); xg [B, N, near*P*P] = tokens * mask, mask [B, N] as
+ *   vc_s2eft_gate_fwd's on tokens.  A token's mean is its slots' band sums added in slot order over
+ *   (float)(near*P*P), its max the fmaxf chain of the band maxima: a mask can differ from vc_s2eft_gate_fwd's on
+ *   materialised tokens only where the sigmoid is within fp32 rounding of beta.  w null: no gate (xg = tokens,
+ *   mask = 1 where mask is given; bias and mask may be null).  N <= 4096, N*near*P*P < 2^31.
  * vc_s2eft_cls_rows: X[b,0,:] = cls + pos[0] (:150-152); vc_s2eft_strip_cls: dE = dX[:,1:,:].
  * vc_s2eft_attn_fwd/bwd: Attention :45-74 core, dim_head 16, softmax(q k^T * scale) v over
  *   qkv [B*T, 3*H*16] (to_qkv output, q|k|v blocks); out [B*T, H*16]; lse [B,H,T] saved; T <= 256.
@@ -555,6 +564,9 @@ VC_API int vc_confusion_matrix(long n, const long long* target, const long long*
  *   weight viewed [T, 2T] over Z[b] = interleave(x, last) [2T, D]; biasmat [T, D] = bias broadcast. */
 VC_API int vc_s2eft_gate_fwd(int B, int N, int C, const float* x, const float* w, const float* bias, float beta,
                              float* xg, float* mask, hipStream_t stream);
+VC_API int vc_s2eft_patch_gate_fwd(int B, int C1, int C2, int P, int near, const float* x1, const float* x2,
+                                   const float* w, const float* bias, float beta, float* xg, float* mask,
+                                   hipStream_t stream);
 VC_API int vc_s2eft_cls_rows(int B, int T, int D, const float* cls, const float* pos, float* X, hipStream_t stream);
 VC_API int vc_s2eft_strip_cls(int B, int N, int D, const float* dX, float* dE, hipStream_t stream);
 VC_API int vc_s2eft_attn_fwd(int B, int T, int H, const float* qkv, float scale, float* out, float* lse,

@@ -1,9 +1,10 @@
 """GPU tool: `TrainStepper.step` of the comparison models with `capture_step` False (the eager sequence) and True (one
 hipGraph replay per batch, the dropout seed advanced on the device) at B = 64 with dropout 0.1: HCTnet (patch 11, 16
-classes, 6 tokens), MFT (30 bands, patch 11) and SpectralFormer (144 + 1 bands).  Per model and mode: the median step
+classes, 6 tokens), MFT (30 bands, patch 11), SpectralFormer (144 + 1 bands) and S2EFT (144 + 1 bands, patch 7, over
+the two patches).  Per model and mode: the median step
 time of 300 steps after 5 (each ended by a device synchronise, host clock, as tools/hct_step.py) and the kernel launches
 per step (torch.profiler, a separate pass of 5 steps).  DESIGN.md section 23 records the output.
-usage: python tools/train_capture.py [MODEL ...] [K]     MODEL: hctnet | mft | spectralformer (default: all), K steps (300)"""
+usage: python tools/train_capture.py [MODEL ...] [K]     MODEL: hctnet | mft | spectralformer | s2eft (default: all), K steps (300)"""
 import os
 import statistics
 import sys
@@ -47,6 +48,10 @@ def build(tag, dev):
         m = MFT(patch_size=11, FM=16, NC=30, NCLidar=1, Classes=16, HSIOnly=False).to(dev)
         opt = Adam(m.parameters(), lr=5e-4, weight_decay=5e-3)
         shapes = ((30, 11, 11), (1, 11, 11))
+    elif tag == "s2eft":
+        m, opt, crit, _ = mu.get_model("S2EFT", n_classes=16, n_bands=(144, 1), ignored_labels=[0],
+                                       dataset="Houston2013", device=dev)
+        shapes = ((144, 7, 7), (1, 7, 7))
     else:
         m, opt, crit, _ = mu.get_model("SpectralFormer", n_classes=16, n_bands=(144, 1), ignored_labels=[0],
                                        dataset="Houston2013", device=dev)
@@ -97,8 +102,8 @@ def run(tag, k):
 def main():
     args = sys.argv[1:]
     k = int(args.pop()) if args and args[-1].isdigit() else 300
-    for tag in args or ["hctnet", "mft", "spectralformer"]:
-        if tag not in ("hctnet", "mft", "spectralformer"):
+    for tag in args or ["hctnet", "mft", "spectralformer", "s2eft"]:
+        if tag not in ("hctnet", "mft", "spectralformer", "s2eft"):
             raise SystemExit(f"unknown model {tag}")
         run(tag, k)
 

@@ -85,6 +85,134 @@ __global__ __launch_bounds__(512) void gate_fwd(int N, int C, const float* __res
   for (int i = per * blockIdx.y + threadIdx.x; i < end; i += 512) xgb[i] = xb[i] * msk[i / C];
 }
 
+// ------------------------------------------------------------------ spectral gate straight from the two patches
+// tokens[b, j, s*PP + p] = r[b, (j + s - near/2) mod N, p], r = cat(x1, x2) over the channel axis [B, N, PP]
+// (PP = P*P, N = C1 + C2): band j's row is (previous, this, next band), wrapping at both ends.  The token tensor is
+// never stored.  Blocks (sample, slice): a slice is a contiguous 1/gridDim.y of the sample's N*near*PP output floats,
+// rows j0 .. j1.  The block forms the per-BAND sum and max over PP of the bands its rows' gate reads -- tokens
+// j0 - 3 .. j1 + 3 of the k=7 conv (zero padded at the ends of the token axis) and their neighbour bands (circular),
+// at most N -- one wave per band, GR bands in flight, kept in LDS under the band's index; a band's statistics are the
+// same bits in every block.  A token's mean is its `near` band sums added in slot order over (float)(near*PP), its
+// max an fmaxf chain over the slots; then gate_fwd's conv / sigmoid / threshold for rows j0 .. j1 (the block holding a
+// row's first float writes its mask).  Output float i of a sample: segment seg = i / PP = j*near + s, pixel i % PP; a
+// segment is PP contiguous floats on both sides.  w == nullptr: no gate (xg = tokens, mask = 1 where given).
+// Scalar loads and stores: rows of near*PP floats (147) and bands of PP floats (49) are not 16-B aligned.
+__global__ __launch_bounds__(512) void patch_gate_fwd(int C1, int C2, FastDiv dpp, int near,
+                                                      const float* __restrict__ x1, const float* __restrict__ x2,
+                                                      const float* __restrict__ w, const float* __restrict__ bias,
+                                                      float beta, float* __restrict__ xg, float* __restrict__ mask) {
+  extern __shared__ float sh[];
+  const int N = C1 + C2, nn = near >> 1, PP = (int)dpp.div, C = near * PP;
+  float* bsum = sh;
+  float* bmax = sh + N;
+  float* msk = sh + 2 * N;
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long total = (long)N * C;   // < 2^31 (host check)
+  const long per = (total + gridDim.y - 1) / gridDim.y;
+  const long begin = per * blockIdx.y, end = min(total, begin + per);
+  if (begin >= end) return;         // the whole block (no barrier was passed)
+  const int j0 = (int)(begin / C), j1 = (int)((end - 1) / C);
+  const float* x1b = x1 + (long)b * C1 * PP;
+  const float* x2b = C2 > 0 ? x2 + (long)b * C2 * PP : nullptr;
+  auto band = [&](int n) { return n < C1 ? x1b + (long)n * PP : x2b + (long)(n - C1) * PP; };
+  if (w != nullptr) {
+    // bands first, first + 1, ... (mod N), cnt of them: those of tokens max(0, j0 - 3) .. min(N - 1, j1 + 3)
+    const int ta = max(0, j0 - 3), tb = min(N - 1, j1 + 3);
+    const int cnt = min(N, tb - ta + 1 + 2 * nn);
+    const int first = ta - nn < 0 ? ta - nn + N : ta - nn;
+    constexpr int GR = 4;
+    for (int i0 = wave; i0 < cnt; i0 += 8 * GR) {
+      int n[GR];
+      float v[GR];
+#pragma unroll
+      for (int g = 0; g < GR; ++g) {
+        n[g] = first + i0 + 8 * g;
+        if (n[g] >= N) n[g] -= N;
+        v[g] = (i0 + 8 * g < cnt && lane < PP) ? band(n[g])[lane] : 0.f;
+      }
+      float s[GR], m[GR];
+#pragma unroll
+      for (int g = 0; g < GR; ++g) {
+        s[g] = 0.f;
+        m[g] = -INFINITY;
+        if (lane < PP) {
+          s[g] = v[g];
+          m[g] = v[g];
+        }
+        if (i0 + 8 * g < cnt)
+          for (int p = lane + 64; p < PP; p += 64) {   // pixels beyond one wave (P >= 9)
+            const float vv = band(n[g])[p];
+            s[g] += vv;
+            m[g] = fmaxf(m[g], vv);
+          }
+      }
+#pragma unroll
+      for (int g = 0; g < GR; ++g) {
+        s[g] = wave_sum(s[g]);
+        m[g] = wave_max(m[g]);
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (int g = 0; g < GR; ++g)
+          if (i0 + 8 * g < cnt) {
+            bsum[n[g]] = s[g];
+            bmax[n[g]] = m[g];
+          }
+      }
+    }
+    __syncthreads();
+    const float cnt_f = (float)C;
+    auto stat = [&](int j, float& a, float& m) {   // token j's mean and max from its bands' statistics
+      int n = j - nn;
+      if (n < 0) n += N;
+      float s = 0.f;
+      m = -INFINITY;
+      for (int sl = 0; sl < near; ++sl) {
+        s += bsum[n];
+        m = fmaxf(m, bmax[n]);
+        if (++n == N) n = 0;
+      }
+      a = s / cnt_f;
+    };
+    for (int t = j0 + threadIdx.x; t <= j1; t += 512) {
+      float v = bias[0];
+      for (int k = 0; k < 7; ++k) {
+        const int j = t + k - 3;
+        if (j >= 0 && j < N) {
+          float a, m;
+          stat(j, a, m);
+          v += w[k] * a + w[7 + k] * m;
+        }
+      }
+      const float s = 1.0f / (1.0f + expf(-v));
+      const float m = s >= beta ? 1.0f : 0.0f;
+      msk[t] = m;
+      if ((long)t * C >= begin) mask[(long)b * N + t] = m;
+    }
+    __syncthreads();
+  } else if (mask != nullptr) {
+    for (int t = j0 + threadIdx.x; t <= j1; t += 512)
+      if ((long)t * C >= begin) mask[(long)b * N + t] = 1.0f;
+  }
+  float* xgb = xg + (long)b * total;
+  auto src = [&](long i, int& j) {   // the input float behind output float i, and its row
+    int p;
+    const int seg = fdivmod((int)i, dpp, p);
+    j = near == 3 ? seg / 3 : seg;
+    int n = seg - j * near + j - nn;
+    n = n < 0 ? n + N : (n >= N ? n - N : n);
+    return band(n)[p];
+  };
+  for (long i = begin + threadIdx.x; i < end; i += 1024) {   // two floats per thread in flight
+    const long i2 = i + 512;
+    int ja, jb = 0;
+    const float va = src(i, ja);
+    const float vb = i2 < end ? src(i2, jb) : 0.f;
+    xgb[i] = w != nullptr ? va * msk[ja] : va;
+    if (i2 < end) xgb[i2] = w != nullptr ? vb * msk[jb] : vb;
+  }
+}
+
 // X[b, 0, :] = cls + pos[0]  (the other rows come from the embedding GEMM with pos fused as addend)
 __global__ void cls_rows(int B, int T, int D, const float* __restrict__ cls, const float* __restrict__ pos,
                          float* __restrict__ X) {
@@ -480,6 +608,24 @@ VC_API int vc_s2eft_gate_fwd(int B, int N, int C, const float* x, const float* w
   VC_REQUIRE(B > 0 && N > 0 && C > 0 && N <= 4096);
   VC_REQUIRE_I32((long)N * C);
   hipLaunchKernelGGL(gate_fwd, dim3(B, 8), dim3(512), 3 * N * sizeof(float), stream, N, C, x, w, bias, beta, xg, mask);
+  VC_CHECK_LAUNCH();
+  return VC_OK;
+}
+
+VC_API int vc_s2eft_patch_gate_fwd(int B, int C1, int C2, int P, int near, const float* x1, const float* x2,
+                                   const float* w, const float* bias, float beta, float* xg, float* mask,
+                                   hipStream_t stream) {
+  VC_REQUIRE(B > 0 && C1 >= 1 && C2 >= 0 && P >= 1 && (near == 1 || near == 3));
+  VC_REQUIRE((long)C1 + C2 <= 4096);
+  const long N = (long)C1 + C2, PP = (long)P * P;
+  VC_REQUIRE_I32(PP);
+  VC_REQUIRE_I32(N * near * PP);
+  VC_REQUIRE(x1 && xg && (C2 == 0 || x2));
+  VC_REQUIRE(w == nullptr || (bias && mask));   // w == nullptr: the ungated call (xg = tokens)
+  // slices of at least 1024 output floats, 16 at the most (config 5: 16 of 1333 floats, 10 rows and 18 bands each)
+  const int slices = (int)std::min(16L, (N * near * PP + 1023) / 1024);
+  hipLaunchKernelGGL(patch_gate_fwd, dim3(B, slices), dim3(512), 3 * N * sizeof(float), stream, C1, C2,
+                     make_fastdiv((uint32_t)PP), near, x1, x2, w, bias, beta, xg, mask);
   VC_CHECK_LAUNCH();
   return VC_OK;
 }

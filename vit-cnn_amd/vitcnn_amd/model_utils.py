@@ -116,15 +116,18 @@ def get_model(name, **kwargs):
 def _get_s2eft(n_bands, n_classes, device, kwargs):
     """S2EFT branch of model_utils.py:400-423 (config 5): ViT(image_size=patch_size, near_band 3,
     num_patches=n_bands, dim 64, depth 5, heads 4, mlp_dim 8, dropout 0.1, mode 'CAF'), Adam(lr 5e-4),
-    weighted CE, epoch 600, batch 64.  Adam = the fused AdamW kernel with weight_decay 0.  The model
-    takes x [B, n_bands + 1, patch_size**2 * 3]."""
-    from .s2eft import ViT
+    weighted CE, epoch 600, batch 64.  Adam = the fused AdamW kernel with weight_decay 0.  The model is
+    `s2eft.S2EFT`, the reference's `ViT` over the two patches: forward(x1 [B, n_bands, P, P], x2 [B, 1, P, P]) forms
+    the neighbour-band token rows [B, n_bands + 1, patch_size**2 * 3] on the device (SURVEY.md section 8 row A13,
+    DESIGN.md section 26), so `train` / `val` / `test` run it like every other model (one LiDAR band, as the
+    reference's num_patches = n_bands implies)."""
+    from .s2eft import S2EFT
     kwargs.setdefault("patch_size", 7)
     kwargs.setdefault("applyPCA", False)
     if kwargs["applyPCA"]:
         n_bands = 30
-    model = ViT(image_size=kwargs["patch_size"], near_band=3, num_patches=n_bands, num_classes=n_classes, dim=64,
-                depth=5, heads=4, mlp_dim=8, dropout=0.1, emb_dropout=0.1, mode="CAF").to(device)
+    model = S2EFT(image_size=kwargs["patch_size"], near_band=3, num_patches=n_bands, num_classes=n_classes, dim=64,
+                  depth=5, heads=4, mlp_dim=8, dropout=0.1, emb_dropout=0.1, mode="CAF").to(device)
     lr = kwargs.setdefault("lr", 0.0005)
     optimizer = AdamW(model.parameters(), lr=lr, weight_decay=0.0)
     criterion = CrossEntropyLoss(weight=kwargs["weights"])
@@ -309,7 +312,7 @@ def train(savename, run, bands, net, optimizer, criterion, data_loader, epoch, s
 
     The step is `vitcnn_amd.step.TrainStepper.step`: for ViT-CNN with the fused AdamW one hipGraph
     replay per batch (captured per batch shape; data parallel: bucketed RCCL all-reduce inside it);
-    with `capture_step=True` also for the comparison models (MFT, HCTnet, MDL-RS, EndNet, SpectralFormer,
+    with `capture_step=True` also for the comparison models (MFT, HCTnet, MDL-RS, EndNet, SpectralFormer, S2EFT,
     FusAtNet with the fused optimizer and the package's losses; the dropout masks' seed then lives in device memory
     and every replay draws fresh masks: seeds.py).  `last_stats["launch"]` names the path.
     The per-iteration losses stay on the device and are read in one transfer at each display point

@@ -11,6 +11,13 @@ and `.pth` files interchange.  Forward and backward are one hand-written program
 parameters live in one flat fp32 buffer whose `.grad` the backward fills (the fused optimizer of
 `optim.py` then updates it in one pass; Adam = `AdamW(weight_decay=0)`).
 
+Two classes share the tree and the program.  `ViT` is the reference's class: forward(x) over ready-made token
+rows x [B, n_bands + 1, P*P*near_band].  `S2EFT` is the two-input model `get_model("S2EFT")` builds, the one
+`train` / `val` / `test` can run: forward(x1 [B, C1, P, P], x2 [B, C2, P, P]) forms the circular neighbour-band
+token rows of the authors' data preparation (band j's row = previous, this, next band of cat(x1, x2), wrapping at
+both ends) inside the gate kernel (`vc_s2eft_patch_gate_fwd`), so the ungated token tensor never exists
+(DESIGN.md section 26); `neighbour_band_tokens` returns it for callers who want the rows.
+
 Dropout (p = 0.1 in `get_model`) is applied in training at the reference's four sites (emb_dropout
 :151, to_out :43, FeedForward :26 and :28) by a counter-based hash mask (`vc_dropout_fwd`, seeded
 from torch's CPU generator each forward, so `torch.manual_seed` reproduces a run; a hipGraph replay
@@ -32,6 +39,7 @@ from ._lib import lib
 from .flat import F32, FlatParams
 
 LN_EPS = 1e-5  # nn.LayerNorm default (PreNorm :13-19, mlp_head :125-128)
+GATE_BETA = 0.4  # the spectral gate's threshold (:142)
 
 
 # ---------------------------------------------------------------- parameter tree (reference names)
@@ -104,6 +112,7 @@ class ViT(FlatParams, nn.Module):
         self.N, self.C, self.D, self.depth, self.heads = num_patches + 1, patch_dim, dim, depth, heads
         self.hidden, self.ncls, self.mode = mlp_dim, num_classes, mode
         self.p_drop, self.p_emb = float(dropout), float(emb_dropout)
+        self.image_size, self.near = int(image_size), int(near_band)
         self._build_flat()
 
     # ------------------------------------------------------------ forward
@@ -115,6 +124,50 @@ class ViT(FlatParams, nn.Module):
         if x.dim() != 3 or x.shape[1] != self.N or x.shape[2] != self.C:
             raise RuntimeError(f"expected x [B, {self.N}, {self.C}], got {list(x.shape)}")
         return program.run(self, _Program, x.detach().to(torch.float32).contiguous())
+
+
+class S2EFT(ViT):
+    """`ViT` (same constructor, parameter tree and initialisation draws) over the two patches:
+    forward(x1 [B, C1, P, P], x2 [B, C2, P, P]) -> logits, with C1 + C2 = num_patches + 1 and P = image_size.
+    near_band must be 1 or 3 (the token kernel's neighbourhoods)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.near not in (1, 3):
+            raise ValueError(f"S2EFT MI355X path: near_band must be 1 or 3, got {self.near}")
+
+    def forward(self, x1: torch.Tensor, x2: torch.Tensor, mask=None) -> torch.Tensor:
+        if mask is not None:
+            raise NotImplementedError("S2EFT mask path is not supported (the reference's raises NameError, :58)")
+        if x1.device.type != "cuda" or x2.device.type != "cuda":
+            raise RuntimeError("S2EFT MI355X path: inputs must be on a ROCm (cuda) device; no CPU fallback")
+        P = self.image_size
+        ok = (x1.dim() == 4 and x2.dim() == 4 and x1.shape[0] == x2.shape[0] and x1.shape[1] >= 1
+              and x1.shape[1] + x2.shape[1] == self.N and tuple(x1.shape[2:]) == (P, P)
+              and tuple(x2.shape[2:]) == (P, P))
+        if not ok:
+            raise RuntimeError(f"expected x1 [B, C1, {P}, {P}] and x2 [B, C2, {P}, {P}] with C1 + C2 = {self.N} "
+                               f"(token rows of {self.near} * {P} * {P} = {self.C}), got {list(x1.shape)} / "
+                               f"{list(x2.shape)}")
+        return program.run(self, _PatchProgram, x1.detach().to(torch.float32).contiguous(),
+                           x2.detach().to(torch.float32).contiguous())
+
+
+def neighbour_band_tokens(x1: torch.Tensor, x2: torch.Tensor, near_band: int = 3) -> torch.Tensor:
+    """The ungated token rows [B, N, near_band * P * P] (N = C1 + C2) of x1 [B, C1, P, P] and x2 [B, C2, P, P] on the
+    device: tokens[b, j, s*P*P + p] = cat(x1, x2)[b, (j + s - near_band // 2) mod N, p] -- what `S2EFT.forward` feeds
+    its gate, for callers of `ViT` who want the rows (the ungated call of `vc_s2eft_patch_gate_fwd`)."""
+    if x1.device.type != "cuda" or x2.device != x1.device:
+        raise RuntimeError("neighbour_band_tokens: inputs must be on one ROCm (cuda) device; no CPU fallback")
+    if x1.dim() != 4 or x2.dim() != 4 or x1.shape[2] != x1.shape[3] or x2.shape[0] != x1.shape[0] \
+            or (x2.shape[1] > 0 and x2.shape[2:] != x1.shape[2:]):
+        raise RuntimeError(f"expected x1 [B, C1, P, P] and x2 [B, C2, P, P], got {list(x1.shape)} / {list(x2.shape)}")
+    x1, x2 = x1.detach().to(torch.float32).contiguous(), x2.detach().to(torch.float32).contiguous()
+    B, C1, P, C2 = x1.shape[0], x1.shape[1], x1.shape[2], x2.shape[1]
+    out = torch.empty(B, C1 + C2, int(near_band) * P * P, dtype=torch.float32, device=x1.device)
+    lib().vc_s2eft_patch_gate_fwd(B, C1, C2, P, int(near_band), x1.data_ptr(), x2.data_ptr() if C2 else None, None,
+                                  None, 0.0, out.data_ptr(), None, torch.cuda.current_stream(x1.device).cuda_stream)
+    return out
 
 
 # the backward's parameter gradients (round 6): 0 = each on the chain where its inputs are made; 1 = each on a side
@@ -166,9 +219,7 @@ class _Program(program.Program):
         L, B, T, N, C, D = self.L, self.B, self.T, self.m.N, self.m.C, self.m.D
         R = B * T
         P = self.P
-        xg, mask = self.new(B, N, C), self.new(B, N)
-        L.vc_s2eft_gate_fwd(B, N, C, self.x.data_ptr(), P["conv2d.weight"], P["conv2d.bias"], 0.4, xg.data_ptr(),
-                            mask.data_ptr(), self.s)
+        xg = self.gate()
         X = self.new(B, T, D)
         L.vc_s2eft_cls_rows(B, T, D, P["cls_token"], P["pos_embedding"], X.data_ptr(), self.s)
         # rows 1..N of every sample: xg W^T + b + pos[1 + t]  (pos fused as the GEMM's row addend)
@@ -179,6 +230,14 @@ class _Program(program.Program):
             self.drop("emb", X, None, X, R * D, self.pe)
         self.xg = xg
         return X
+
+    def gate(self):
+        """the gated token rows xg [B, N, C] of the input (the first launch of `embed`)"""
+        L, B, N, C, P = self.L, self.B, self.m.N, self.m.C, self.P
+        xg, mask = self.new(B, N, C), self.new(B, N)
+        L.vc_s2eft_gate_fwd(B, N, C, self.x.data_ptr(), P["conv2d.weight"], P["conv2d.bias"], GATE_BETA, xg.data_ptr(),
+                            mask.data_ptr(), self.s)
+        return xg
 
     def layers(self, X):
         """the pre-norm encoder layers and the head on the cls row: X [B, T, D] -> logits"""
@@ -441,3 +500,20 @@ class _Program(program.Program):
         if key not in streams:
             streams[key] = torch.cuda.Stream(self.dev)
         return streams[key]
+
+
+class _PatchProgram(_Program):
+    """`_Program` over the two patches: the gate launch reads (x1, x2) and forms the neighbour-band rows itself"""
+
+    def __init__(self, m: S2EFT, needs_grad, x1: torch.Tensor, x2: torch.Tensor):
+        super().__init__(m, needs_grad, x1)
+        self.x2 = x2
+
+    def gate(self):
+        L, B, N, C, P = self.L, self.B, self.m.N, self.m.C, self.P
+        C2 = self.x2.shape[1]
+        xg, mask = self.new(B, N, C), self.new(B, N)
+        L.vc_s2eft_patch_gate_fwd(B, self.x.shape[1], C2, self.m.image_size, self.m.near, self.x.data_ptr(),
+                                  self.x2.data_ptr() if C2 else None, P["conv2d.weight"], P["conv2d.bias"], GATE_BETA,
+                                  xg.data_ptr(), mask.data_ptr(), self.s)
+        return xg

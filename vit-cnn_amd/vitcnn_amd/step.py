@@ -108,8 +108,8 @@ class TrainStepper:
       exactly one update.  A short last batch is simply another shape.  The optimizer's
       hyper-parameters live in device memory and are synced before each replay (`AdamW.sync_hyper`),
       so StepLR's lr changes take effect as with torch.optim.
-    * anything else (torch modules / optimizers, S2EFT's one-input forward, FusAtNet): the reference's
-      eager sequence, with `parallel.allreduce_gradients` between backward and step under DP.
+    * anything else (torch modules / optimizers, `s2eft.ViT`'s one-input forward over token rows, FusAtNet):
+      the reference's eager sequence, with `parallel.allreduce_gradients` between backward and step under DP.
     * `capture_step=True` (opt-in): the comparison models -- a flat-parameter model other
       than ViT-CNN with a two-input forward, stepped by the fused AdamW / Adam under one of the package's losses --
       follow the same protocol through autograd: the first batch of a shape runs `zero_grad; crit(net(x1, x2),
