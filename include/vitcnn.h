@@ -859,4 +859,34 @@ VC_API int vc_hct_ctattn_fwd_ds(int B, int T, const float* X, long strideX, cons
                                 float pp0, float po0, float pp1, float po1, const unsigned long long* seed_dev,
                                 unsigned long long site_offset, float* out, unsigned char* mask, hipStream_t stream);
 
+/* ---------------------------------------------------------------- principal components (csrc/pca.hip)
+ * The whitened PCA of the HSI cube's pixel spectra (utils.py:85-93 applyPCA, scikit-learn on the host in the reference)
+ * as three device ops; the C x C eigendecomposition between them stays on the host (vitcnn_amd/pca.py).  Operands are
+ * the rows of an [n, C] fp32 matrix x with leading dimension ld >= C: the [W, H, C] cube with n = W * H, ld = C.
+ * Limits: 2 <= n < 2^31 - 64, 1 <= C <= 512, 1 <= K <= min(C, 64), ld >= C, ldy >= K; anything else returns 1 before any
+ * launch.  No floating-point atomics: a second call gives the same bits.  Columns ld > C, an unaligned base and
+ * C % 4 != 0 are all accepted; nothing outside the logical operands is read into a result.
+ *
+ * vc_pca_slab_rows: R, the rows of x one block of vc_pca_cov accumulates in fp32 (returned, not a status).
+ * vc_pca_cov_workspace: *bytes the caller provides as `workspace` (16-B aligned) to vc_pca_mean and vc_pca_cov at this
+ *   n and C (the larger of the two needs: at most 1024 fp64 rows of C, and ceil(n / R) * T (T + 1) / 2 fp32 tiles of
+ *   64 x 64 with T = ceil(C / 64)).
+ * vc_pca_mean: mean[c] = sum_i x[i][c] / n in fp64 -- per-slab partial rows in the workspace (each lane's rows in
+ *   ascending order), then the slabs summed in a fixed order.
+ * vc_pca_cov: cov[C][C] (dense, fp64) = sum_i xc_i xc_i^T / (n - 1), xc_i = x[i] - mean32 formed in registers as the
+ *   panels are staged (rows past n and columns past C stay exactly zero).  Grid: upper-triangle pairs of 64-column
+ *   tiles x slabs of R rows; inner product on v_mfma_f32_16x16x4_f32 (two fma chains of R / 2 per element); one fp32
+ *   tile partial per (slab, pair); a second launch sums the slabs in a fixed order in fp64, divides and mirrors, so cov
+ *   is exactly symmetric.
+ * vc_pca_project: y[i][k] = sum_c (x[i][c] - mean32[c]) wt[c][k], wt [C][K] dense (the whitening folded in by the
+ *   caller), on v_mfma_f32_16x16x4_f32 (one fma chain of C per output), one pass over x with wt held in LDS (128 KB at
+ *   C = 512, K > 32). */
+VC_API int vc_pca_slab_rows(void);
+VC_API int vc_pca_cov_workspace(long n, int C, long* bytes);
+VC_API int vc_pca_mean(long n, int C, long ld, const float* x, void* workspace, double* mean, hipStream_t stream);
+VC_API int vc_pca_cov(long n, int C, long ld, const float* x, const float* mean32, void* workspace, double* cov,
+                      hipStream_t stream);
+VC_API int vc_pca_project(long n, int C, long ld, int K, const float* x, const float* mean32, const float* wt,
+                          float* y, long ldy, hipStream_t stream);
+
 #endif /* VITCNN_H */

@@ -93,6 +93,7 @@ def get_model(name, **kwargs):
     kwargs.setdefault("applyPCA", False)
     if kwargs["applyPCA"]:
         n_bands = 30
+        kwargs.setdefault("pca_components", 30)   # what PatchBatcher / test() must reduce the cube to (pca.py)
     path_type = "multi_clock_gate"
     precision = kwargs.setdefault("precision", "fp32")
     model = Multimodality_Mamba(img_size=patch_size, patch_size=1, stride=1, in_channels1=n_bands,
@@ -126,6 +127,7 @@ def _get_s2eft(n_bands, n_classes, device, kwargs):
     kwargs.setdefault("applyPCA", False)
     if kwargs["applyPCA"]:
         n_bands = 30
+        kwargs.setdefault("pca_components", 30)   # what PatchBatcher / test() must reduce the cube to (pca.py)
     model = S2EFT(image_size=kwargs["patch_size"], near_band=3, num_patches=n_bands, num_classes=n_classes, dim=64,
                   depth=5, heads=4, mlp_dim=8, dropout=0.1, emb_dropout=0.1, mode="CAF").to(device)
     lr = kwargs.setdefault("lr", 0.0005)
@@ -170,6 +172,7 @@ def _get_mft(n_bands, n_bands2, n_classes, device, kwargs):
     kwargs.setdefault("applyPCA", False)
     if kwargs["applyPCA"]:
         n_bands = 30
+        kwargs.setdefault("pca_components", 30)   # what PatchBatcher / test() must reduce the cube to (pca.py)
     model = MFT(patch_size=kwargs["patch_size"], FM=16, NC=n_bands, NCLidar=n_bands2, Classes=n_classes,
                 HSIOnly=False).to(device)
     lr = kwargs.setdefault("lr", 0.0005)
@@ -233,6 +236,7 @@ def _get_spectralformer(n_bands, n_bands2, n_classes, device, kwargs):
     kwargs.setdefault("applyPCA", False)
     if kwargs["applyPCA"]:
         n_bands = 30
+        kwargs.setdefault("pca_components", 30)   # what PatchBatcher / test() must reduce the cube to (pca.py)
     model = SpectralFormer(image_size=kwargs["patch_size"], near_band=1, num_patches=n_bands + n_bands2,
                            num_classes=n_classes, dim=64, depth=5, heads=4, mlp_dim=8, dropout=0.1, emb_dropout=0.1,
                            mode="ViT").to(device)
@@ -256,6 +260,7 @@ def _get_hctnet(n_bands, n_classes, device, kwargs):
     kwargs.setdefault("applyPCA", True)
     if kwargs["applyPCA"]:
         n_bands = 30   # noqa: F841 (as the reference writes it; the constructor takes no band count)
+        kwargs.setdefault("pca_components", 3)   # the model's HSI depth (hctnet.py)
     model = HCTnet(num_classes=n_classes, num_tokens=6, heads=8).to(device)
     lr = kwargs.setdefault("lr", 0.0001)
     optimizer = AdamW(model.parameters(), lr=lr, weight_decay=0.0)
@@ -445,7 +450,13 @@ def test(run, net, img1, img2, hyperparams):
     the reference's `probs`."""
     net.eval()
     if hyperparams.get("applyPCA", False):
-        img1 = apply_pca(img1, 3)   # model_utils.py:1076-1077 (3 components, as the reference)
+        pca, k = hyperparams.get("pca"), hyperparams.get("pca_components", 3)
+        if pca is None:
+            img1 = apply_pca(img1, k)   # model_utils.py:1076-1077 (3 components in the reference), on the host
+        else:   # on the device; passing the training batcher's fitted `batcher.pca` shares one fit (pca.py)
+            from .pca import resolve
+            from .window import _cube
+            img1 = resolve(pca, k, _cube(img1, torch.device(hyperparams["device"])))[1]
     runner = SlidingWindowInference(net, img1, img2, patch_size=hyperparams["patch_size"],
                                     step=hyperparams.get("test_stride", 1), n_classes=hyperparams["n_classes"],
                                     device=hyperparams["device"])

@@ -28,7 +28,14 @@ def window_count(W: int, H: int, P: int, step: int) -> int:
 
 
 def _cube(img, device) -> torch.Tensor:
-    t = torch.as_tensor(np.ascontiguousarray(img, dtype=np.float32))
+    """the [W, H, C] fp32 cube on `device`: from a numpy array (uploaded once) or a float32 tensor (a cube that is
+    already on the device, such as `PCA.transform`'s, is taken as it is)"""
+    if isinstance(img, torch.Tensor):
+        if img.dtype != torch.float32:
+            raise TypeError(f"a cube given as a tensor must be float32, got {img.dtype}")
+        t = img.detach()
+    else:
+        t = torch.as_tensor(np.ascontiguousarray(img, dtype=np.float32))
     if t.dim() == 2:
         t = t.unsqueeze(-1)
     return t.to(device).contiguous()
@@ -86,6 +93,12 @@ class PatchBatcher:
     same `seed` and takes every world-th centre of the padded shuffled list (equal batch counts on every
     rank; `parallel.is_sharded` sees the attributes, so train() does not shard it again).
 
+    `applyPCA=True` reduces the HSI cube to `pca_components` whitened principal components before any patch is cut
+    (MultiModalX, datasets.py:507-508; `get_model` records the count its model needs as `kwargs["pca_components"]`):
+    `pca=None` through scikit-learn on the host as the reference does, `pca="device"` with `vitcnn_amd.pca.PCA` fitted
+    on the uploaded cube, `pca=<PCA object>` with that object (fitted first if it is not).  The fitted object is
+    `self.pca`; handing it to `test()` as `hyperparams["pca"]` shares the one fit.
+
     Augmentations of MultiModalX.__getitem__ (datasets.py:559-568), per sample in the reference's
     order and with its probabilities, the decisions drawn from one host RandomState in the reference's
     call order: flip / rot90 (flip_augmentation, :511-526) folded into the gather; radiation noise
@@ -108,11 +121,16 @@ class PatchBatcher:
     def __init__(self, img1, img2, gt, patch_size: int, ignored_labels=(0,), batch_size: int = 64,
                  flip_augmentation: bool = False, device="cuda", seed: int = 0, rank: int = 0, world: int = 1,
                  name: str = "synthetic", radiation_augmentation: bool = False, mixture_augmentation: bool = False,
-                 applyPCA: bool = False):
+                 applyPCA: bool = False, pca=None, pca_components: int = 3):
         self.device = torch.device(device)
-        if applyPCA:   # MultiModalX (datasets.py:507-508): the HSI cube reduced to 3 components before any patch is cut
-            from .model_utils import apply_pca
-            img1 = apply_pca(np.asarray(img1), 3)
+        self.pca = None
+        if applyPCA:   # MultiModalX (datasets.py:507-508): the HSI cube reduced to its components before any patch is cut
+            if pca is None:   # the reference's host path (scikit-learn)
+                from .model_utils import apply_pca
+                img1 = apply_pca(np.asarray(img1), pca_components)
+            else:             # on the device: "device" fits here, a PCA object is shared (pca.py)
+                from .pca import resolve
+                self.pca, img1 = resolve(pca, pca_components, _cube(img1, self.device))
         self.c1, self.c2 = _cube(img1, self.device), _cube(img2, self.device)
         self.P, self.bs, self.flip = int(patch_size), int(batch_size), bool(flip_augmentation)
         self.radiation, self.mixture = bool(radiation_augmentation), bool(mixture_augmentation)
