@@ -889,4 +889,132 @@ VC_API int vc_pca_cov(long n, int C, long ld, const float* x, const float* mean3
 VC_API int vc_pca_project(long n, int C, long ld, int K, const float* x, const float* mean32, const float* wt,
                           float* y, long ldy, hipStream_t stream);
 
+/* ---------------------------------------------------------------- MHST (csrc/mhst.hip)
+ * model/compare_method/MHST/ (MHST.py, HSPT.py, Pooling.py, PyConv2D.py).  fp32, no floating-point atomics, every sum
+ * in a fixed order: a second call gives the same bits.  Invalid arguments return 1 before any launch.
+ *
+ * vc_mhst_conv_fwd / _dgrad / _wgrad: a grouped 3-D convolution over channels-last rows, spectral stride sd and
+ *   padding pd, square spatial kernel KS (odd, 1..9) with 'same' padding KS / 2 and stride 1:
+ *     x rows (b, d, h, w) of C channels (ldx), w [O][C/G][KD][KS][KS] dense, y rows (b, e, h, w) of O columns (ldy;
+ *     a caller writing one part of a concatenation offsets y and passes the whole row's ldy), Dout = (D + 2 pd - KD) / sd
+ *     + 1 (passed, checked):
+ *     y[b,e,h,w,o] = bias[o] + sum_{kd,kh,kw,c < C/G} w[o][c][kd][kh][kw] x[b, e sd - pd + kd, h - KS/2 + kh,
+ *                    w - KS/2 + kw, (o / (O/G)) (C/G) + c]           (taps outside the map contribute nothing)
+ *   This one family is the model's Conv3d (11,3,3) stride (3,1,1), its four spectral convs (KS 1, each into its 4
+ *   columns of the 16), the 3x3x3 conv, and every PyConv2D branch: a 2-D conv is D = KD = Dout = 1, and the grouped 2-D
+ *   conv over the `(c d)` reshape of the 3-D stage is KD = D, pd = 0, Dout = 1 on the 3-D rows as they are (its weight
+ *   [O][(C/G) D][k][k] IS [O][C/G][D][k][k], and a group of (c d) channels is a group of c since 16 / G is whole).
+ *   dgrad: dx = beta dx + the transposed sum (lddx); wgrad: dw (overwritten) and db (may be null) = column sums of dy,
+ *   H W <= 64 and O / G <= 16 there: one block of 8 waves per (group, input channel, tap), a lane per spatial position,
+ *   the waves splitting the (sample, depth) pairs; per output the wave's xor tree, then the waves in order.
+ * vc_mhst_embed_fwd / _bwd: fusion and token embedding (MHST.py:287-301) from the two pooled maps ph, pl [B,16,64]
+ *   (rows = the 4x4 positions, 64 channels):
+ *     f = wh ph + wl pl;  xcnn[b,j,c] = sum_p W[j][p] f[b,p,c] + bias[j];
+ *     X0[b,0,:] = cls + pos[0];  X0[b,1+j,:] = xcnn[b,j,:] + pos[1+j] + pos[0]     (wh, wl: device scalars)
+ *   bwd from dX0 [B,65,64] and dxcnn [B,64,64] (the CNN classifier's path): dph, dpl and one partial row per sample
+ *   part[b] = [dW 64x16 | dbias 64 | dpos0 64 | dwh, dwl, 0, 0] (VC_MHST_EMBED_PART floats); the caller sums them.
+ * vc_mhst_gate_fwd / _bwd: the head gate (HSPT.py:7-63) on the cls rows x[b] = X + b ldx:
+ *     logits = Wg x + bg [B,16];  train: v = (logits + n) / tau with n = noise_in where given, else Logistic(0,1) noise
+ *     log(u / (1 - u)), u = ((hash(seed, b 16 + h) >> 9) + 0.5) / 2^23 (g1 - g2 of two Gumbel draws is logistic);
+ *     eval: v = logits.  y = sigmoid(v), sel = v > 0.  noise_out (may be null) receives n.
+ *   bwd (straight-through): dlogits = dsel y (1 - y) scale  (scale = 1 / tau in training, 1 in eval).
+ * vc_mhst_headmask_fwd / _bwd: Y[b,t,c] = X[b,t,c] sel[b][(c % 64) / 4] over rows of Wd = 64 or 192 columns (DynaLinear's
+ *   output rows of query | key | value, or the input columns of proj / fc1); bwd: dX = dY sel and
+ *   dsel[b,h] = beta dsel[b,h] + sum_{t, c of head h} dY X  (per column over t ascending, then the head's columns).
+ * vc_mhst_pool_fwd / _bwd: attn_pool (Pooling.py) of q | k | v, X [B,65,192]: per tensor s and head h the depthwise 3x3
+ *   conv (pad 1, its 4 channels shared by the 16 heads) over rows 1..64 as an 8x8 grid, row 0 passed, then LayerNorm(4)
+ *   of every row of every head.  pw = [conv 4x9 | ln.w 4 | ln.b 4] x 3 (VC_MHST_POOL_FLOATS).  A switched-off head is
+ *   computed like any other: its rows come out as ln.b.  bwd: dX and part[b] = the 132 parameter gradients.
+ * vc_mhst_attn_fwd / _bwd: per sample and head (16 heads of width 4) over QKV [B,65,192] (pooled q | k | v):
+ *     a = softmax_j(scale q_i . k_j);  ad = a keep / (1 - p);  o_i = sum_j ad_ij v_j (+ q_i for i >= 1)
+ *   keep = vc_dropout_fwd's hash over the index of mask [B,16,65,65] (bytes, written; may be null at p = 0).  bwd
+ *   recomputes a from QKV, one block per (sample, head) holding the head's 65 x 65 dS and ad in LDS.
+ * vc_mhst_tail_fwd / _bwd: the dual-softmax tail (MHST.py:308-319): avg[b,k] = mean_t z[b,t,k] over z [B,64,32] (ldz),
+ *     p1 = softmax(lg1[b]), p2 = softmax(W2 avg + b2), out = cv p1 + cc p2   (cv, cc device scalars; ncls <= 256)
+ *   bwd: dlg1, dz (lddz) and part[b] = [dW2 ncls x 32 | db2 ncls | dcv, dcc] (ncls * 33 + 2 floats).
+ *
+ * vc_mhst_conv3_fwd / _dgrad / _wgrad: the model's 3x3x3 convolution (16 -> 16 channels, stride 1, padding 1, 8 x 8
+ *   planes; vc_mhst_conv_*'s formulas at C = O = 16, G = 1, KD = KS = 3) as an implicit GEMM on v_mfma_f32_16x16x4_f32:
+ *   K = 27 taps x 16 channels walked tap-major, N = 16, M = B D 64.  fwd and dgrad (dx = beta dx + ...): one block per
+ *   (sample, depth) plane, the weight in LDS; the operand read as float4 runs (x / dy 16-B aligned, ldx / lddy a multiple
+ *   of 4).  wgrad: min(VC_MHST_CONV3_WAVES, B D) waves each walk their planes in order with 27 accumulators (the rows are
+ *   the MFMA's k) and leave a partial [16][16][27] in ws (vc_mhst_conv3_wgrad_ws_floats floats), then summed in wave
+ *   order: a fixed order.  The bias gradient is vc_colsum of dy.
+ *
+ * vc_mhst_hsattn_fwd / _fwd_ds / _bwd: the chain gate -> head mask -> pooling -> attention -> head mask of a head-select
+ *   block FUSED, one block per (sample, head) (each step is independent per head): from the block input's cls rows
+ *   (X, ldx) and the raw q | k | v GEMM output QKV [B,65,192],
+ *     sel, y, noise, logits as vc_mhst_gate_fwd's (noise index b 16 + h; the dot product summed by a wave's xor tree);
+ *     qm = QKV sel (the head's 12 columns);  qp = vc_mhst_pool_fwd(qm);  ao = vc_mhst_attn_fwd(qp) with the same keep
+ *     hash and mask bytes [B,16,65,65];  AM [B,65,64] = ao sel
+ *   with the head's masked and pooled rows in LDS: only AM (and the gate's 4 x [B,16] values, the mask bytes) is written.
+ *   seed_gate / seed_prob: the two sites' seeds (_ds: offsets to *seed_dev).  bwd from dAM: the chain is recomputed from
+ *   QKV, the head's 65 x 65 dS and dropped probabilities sit in LDS; dQKV [B,65,192] (gradient of the raw q | k | v),
+ *   part[(b 16 + h)] = the head's share of the 132 pooling parameter gradients (VC_MHST_POOL_FLOATS per row, B 16 rows;
+ *   the caller sums them in row order), and
+ *     dlogits[b,h] = (dsel_in[b,h] + sum dAM ao + sum dqm QKV) y (1 - y) gscale     (dsel_in: the MLP mask's share, may
+ *   be null; gscale = 1 / tau in training, 1 in eval; the sums in a fixed order). */
+#define VC_MHST_CONV3_WAVES 512
+#define VC_MHST_EMBED_PART 1156
+#define VC_MHST_POOL_FLOATS 132
+VC_API int vc_mhst_conv_fwd(int B, int D, int H, int W, int C, int O, int G, int KD, int KS, int sd, int pd, int Dout,
+                            const float* x, long ldx, const float* w, const float* bias, float* y, long ldy,
+                            hipStream_t stream);
+VC_API int vc_mhst_conv_dgrad(int B, int D, int H, int W, int C, int O, int G, int KD, int KS, int sd, int pd, int Dout,
+                              const float* dy, long lddy, const float* w, float* dx, long lddx, float beta,
+                              hipStream_t stream);
+VC_API int vc_mhst_conv_wgrad(int B, int D, int H, int W, int C, int O, int G, int KD, int KS, int sd, int pd, int Dout,
+                              const float* x, long ldx, const float* dy, long lddy, float* dw, float* db,
+                              hipStream_t stream);
+VC_API int vc_mhst_conv3_fwd(int B, int D, const float* x, long ldx, const float* w, const float* bias, float* y,
+                             long ldy, hipStream_t stream);
+VC_API int vc_mhst_conv3_dgrad(int B, int D, const float* dy, long lddy, const float* w, float* dx, long lddx,
+                               float beta, hipStream_t stream);
+VC_API int vc_mhst_conv3_wgrad_ws_floats(int B, int D);
+VC_API int vc_mhst_conv3_wgrad(int B, int D, const float* x, long ldx, const float* dy, long lddy, float* dw, float* ws,
+                               long ws_floats, hipStream_t stream);
+VC_API int vc_mhst_embed_fwd(int B, const float* ph, const float* pl, const float* wh, const float* wl, const float* W,
+                             const float* bias, const float* pos, const float* cls, float* xcnn, float* X0,
+                             hipStream_t stream);
+VC_API int vc_mhst_embed_bwd(int B, const float* ph, const float* pl, const float* wh, const float* wl, const float* W,
+                             const float* dX0, const float* dxcnn, float* dph, float* dpl, float* part,
+                             hipStream_t stream);
+VC_API int vc_mhst_gate_fwd(int B, const float* X, long ldx, const float* Wg, const float* bg, const float* noise_in,
+                            int train, float tau, unsigned long long seed, float* logits, float* noise_out, float* y,
+                            float* sel, hipStream_t stream);
+VC_API int vc_mhst_gate_fwd_ds(int B, const float* X, long ldx, const float* Wg, const float* bg, const float* noise_in,
+                               int train, float tau, const unsigned long long* seed_dev, unsigned long long site_offset,
+                               float* logits, float* noise_out, float* y, float* sel, hipStream_t stream);
+VC_API int vc_mhst_gate_bwd(int B, const float* dsel, const float* y, float scale, float* dlogits, hipStream_t stream);
+VC_API int vc_mhst_headmask_fwd(int B, int T, int Wd, const float* X, const float* sel, float* Y, hipStream_t stream);
+VC_API int vc_mhst_headmask_bwd(int B, int T, int Wd, const float* dY, const float* X, const float* sel, float* dX,
+                                float* dsel, float beta, hipStream_t stream);
+VC_API int vc_mhst_pool_fwd(int B, const float* X, const float* pw, float eps, float* Y, hipStream_t stream);
+VC_API int vc_mhst_pool_bwd(int B, const float* X, const float* pw, float eps, const float* dY, float* dX, float* part,
+                            hipStream_t stream);
+VC_API int vc_mhst_attn_fwd(int B, const float* QKV, float scale, float p, unsigned long long seed, unsigned char* mask,
+                            float* O, hipStream_t stream);
+VC_API int vc_mhst_attn_fwd_ds(int B, const float* QKV, float scale, float p, const unsigned long long* seed_dev,
+                               unsigned long long site_offset, unsigned char* mask, float* O, hipStream_t stream);
+VC_API int vc_mhst_attn_bwd(int B, const float* QKV, float scale, float p, const unsigned char* mask, const float* dO,
+                            float* dQKV, hipStream_t stream);
+VC_API int vc_mhst_hsattn_fwd(int B, const float* X, long ldx, const float* Wg, const float* bg, const float* noise_in,
+                              int train, float tau, unsigned long long seed_gate, unsigned long long seed_prob,
+                              const float* QKV, const float* pw, float eps, float scale, float p, unsigned char* mask,
+                              float* logits, float* noise_out, float* y, float* sel, float* AM, hipStream_t stream);
+VC_API int vc_mhst_hsattn_fwd_ds(int B, const float* X, long ldx, const float* Wg, const float* bg,
+                                 const float* noise_in, int train, float tau, const unsigned long long* seed_dev,
+                                 unsigned long long gate_offset, unsigned long long prob_offset, const float* QKV,
+                                 const float* pw, float eps, float scale, float p, unsigned char* mask, float* logits,
+                                 float* noise_out, float* y, float* sel, float* AM, hipStream_t stream);
+VC_API int vc_mhst_hsattn_bwd(int B, const float* QKV, const float* sel, const float* y, const float* pw, float eps,
+                              float scale, float p, const unsigned char* mask, const float* dAM, const float* dsel_in,
+                              float gscale, float* dQKV, float* part, float* dlogits, hipStream_t stream);
+VC_API int vc_mhst_tail_fwd(int B, int ncls, const float* lg1, const float* z, long ldz, const float* W2,
+                            const float* b2, const float* cv, const float* cc, float* p1, float* p2, float* avg,
+                            float* out, hipStream_t stream);
+VC_API int vc_mhst_tail_bwd(int B, int ncls, const float* dout, const float* p1, const float* p2, const float* avg,
+                            const float* W2, const float* cv, const float* cc, float* dlg1, float* dz, long lddz,
+                            float* part, hipStream_t stream);
+
 #endif /* VITCNN_H */

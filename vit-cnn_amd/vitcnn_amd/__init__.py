@@ -13,7 +13,8 @@ from .endnet import EndNet  # noqa: F401
 from .spectralformer import SpectralFormer  # noqa: F401
 from .hctnet import HCTnet  # noqa: F401
 from .s2eft import S2EFT  # noqa: F401
+from .mhst import MHST  # noqa: F401
 
 __all__ = ["Multimodality_Mamba", "CrossEntropyLoss", "Cross_fusion_CNN_Loss", "AdamW", "Adam", "MFT", "Early_fusion_CNN",
            "Middle_fusion_CNN", "Late_fusion_CNN", "Cross_fusion_CNN", "EndNet", "SpectralFormer", "HCTnet",
-           "S2EFT", "EndNet_Loss", "fused_train_step"]
+           "S2EFT", "MHST", "EndNet_Loss", "fused_train_step"]

@@ -15,7 +15,8 @@ Registered: "Multimodality_Mamba" (the README's "ViT-CNN (ours)"), "S2EFT" (conf
 "Middle_fusion_CNN", "Late_fusion_CNN" and "Cross_fusion_CNN" (:69-108; the last trains with
 `Cross_fusion_CNN_Loss` over its three outputs, and `val` / `test` read the first), and the per-pixel models
 "EndNet" (:119-128, `EndNet_Loss` over its five outputs) and "SpectralFormer" (:377-399), both with patch_size 1, and
-"HCTnet" (:351-363; the HSI cube reduced to 3 principal components, `PatchBatcher(applyPCA=True)`).
+"HCTnet" (:351-363; the HSI cube reduced to 3 principal components, `PatchBatcher(applyPCA=True)`) and "MHST"
+(:314-335; patch_size 8, the one even patch side).
 The reference's other branches import modules absent from the reference tree (SURVEY.md section 2a
 row 22) and are out of scope for this path.
 
@@ -47,7 +48,7 @@ from .optim import AdamW
 from .window import SlidingWindowInference
 
 MDLRS = ("Early_fusion_CNN", "Middle_fusion_CNN", "Late_fusion_CNN", "Cross_fusion_CNN")
-REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT") + MDLRS + ("EndNet", "SpectralFormer", "HCTnet")
+REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT") + MDLRS + ("EndNet", "SpectralFormer", "HCTnet", "MHST")
 
 
 def camel_to_snake(name: str) -> str:
@@ -86,6 +87,8 @@ def get_model(name, **kwargs):
         return _get_spectralformer(n_bands, n_bands2, n_classes, device, kwargs)
     if name == "HCTnet":
         return _get_hctnet(n_bands, n_classes, device, kwargs)
+    if name == "MHST":
+        return _get_mhst(n_bands, n_bands2, n_classes, device, kwargs)
     kwargs.setdefault("patch_size", 9)
     patch_size = kwargs["patch_size"]
     center_pixel = True
@@ -266,6 +269,31 @@ def _get_hctnet(n_bands, n_classes, device, kwargs):
     optimizer = AdamW(model.parameters(), lr=lr, weight_decay=0.0)
     criterion = CrossEntropyLoss(weight=kwargs["weights"])
     kwargs.setdefault("epoch", 100)
+    kwargs.setdefault("batch_size", 64)
+    kwargs.setdefault("supervision", "full")
+    kwargs["center_pixel"] = True
+    return model, optimizer, criterion, kwargs
+
+
+def _get_mhst(n_bands, n_bands2, n_classes, device, kwargs):
+    """MHST branch of model_utils.py:314-335: MHST(l1, l2, patch 8, width 64, en_depth 5 of 4 heads, mlp_dim 8, dropout
+    0.1, coefficient_hsi 0.6, coefficient_vit 0.7, 8 head-select blocks of 16 heads, tau 5, no qkv bias, mlp_ratio 4),
+    AdamW(lr 8e-4), weighted CE over the model's mixture of probabilities, epoch 1000, batch 64; under applyPCA the
+    model is built for 30 bands."""
+    from .mhst import MHST
+    kwargs.setdefault("patch_size", 8)
+    kwargs.setdefault("applyPCA", False)
+    if kwargs["applyPCA"]:
+        n_bands = 30
+        kwargs.setdefault("pca_components", 30)   # what PatchBatcher / test() must reduce the cube to (pca.py)
+    model = MHST(l1=n_bands, l2=n_bands2, patch_size=kwargs["patch_size"], num_patches=64, num_classes=n_classes,
+                 encoder_embed_dim=64, en_depth=5, en_heads=4, mlp_dim=8, dropout=0.1, emb_dropout=0.1,
+                 coefficient_hsi=0.6, coefficient_vit=0.7, hsp_vit_depth=8, hsp_vit_num_heads=16, head_tau=5,
+                 use_head_select=True, vit_qkv_bias=False, mlp_ratio=4, attnproj_mlp_drop=0.1, attn_drop=0.1).to(device)
+    lr = kwargs.setdefault("lr", 8e-4)
+    optimizer = AdamW(model.parameters(), lr=lr)
+    criterion = CrossEntropyLoss(weight=kwargs["weights"])
+    kwargs.setdefault("epoch", 1000)
     kwargs.setdefault("batch_size", 64)
     kwargs.setdefault("supervision", "full")
     kwargs["center_pixel"] = True

@@ -114,7 +114,8 @@ def state_for(model, device) -> SeedState | None:
 
 
 def has_dropout(model) -> bool:
-    """does a training forward of `model` draw a mask (an nn.Dropout with p > 0, or the ViT models' p_drop / p_emb)"""
-    if getattr(model, "p_drop", 0.0) > 0 or getattr(model, "p_emb", 0.0) > 0:
+    """does a training forward of `model` draw a mask (an nn.Dropout with p > 0, or the ViT models' p_drop / p_emb) or
+    other noise from the step seed (`draws_noise`: MHST's head gates)"""
+    if getattr(model, "draws_noise", False) or getattr(model, "p_drop", 0.0) > 0 or getattr(model, "p_emb", 0.0) > 0:
         return True
     return any(isinstance(m, torch.nn.Dropout) and m.p > 0 for m in model.modules())
