@@ -1017,4 +1017,80 @@ VC_API int vc_mhst_tail_bwd(int B, int ncls, const float* dout, const float* p1,
                             const float* W2, const float* cv, const float* cc, float* dlg1, float* dz, long lddz,
                             float* part, hipStream_t stream);
 
+/* ---------------------------------------------------------------- GLT-Net (the global-local transformer comparison model)
+ * model/compare_method/GLT_Net/GLT_Net.py over channels-last rows; P = the model's patch side (even, 2 <= P <= 8 for
+ * the fusion kernels), NP = P^2, T = NP + 1, token width 64.  The model's three scales P, 2P, 3P are the centre crops
+ * of ONE 3P patch.  All fp32; no float atomics; every sum runs in a fixed order (two runs are bit-identical).
+ *
+ * vc_glt_crops: x [B, C, 3P, 3P] (NCHW) -> the three centre crops as channels-last rows of ld >= C floats, columns
+ *   C .. ld - 1 written 0:  r_k[(b, i, j)][c] = x[b, c, i + o_k, j + o_k],  i, j < k P,  o_1 = P, o_2 = P / 2, o_3 = 0.
+ *   One launch; the rows are conv inputs and MSE targets; there is no backward.
+ *
+ * vc_glt_fuse_fwd / _bwd: fusion, spatial embedding, SA-GDR and the token buffer, one block per sample.  From the
+ *   2x2-max-pooled maps of the two modalities at the three scales, pa_k, pb_k [B, n_k, 64], n_k = (k P / 2)^2 (rows =
+ *   pooled positions), and device scalars xs1, xs2:
+ *     f_k = xs1 pa_k + xs2 pb_k;      e_k[b, j, c] = bias_k[j] + sum_p W_k[j][p] f_k[b, p, c]     (W_k [NP, n_k])
+ *     avg = (e_1 + e_2 + e_3) / 3;    mx = max(e_1, e_2, e_3)                                     (per (b, j, c))
+ *     g[b, j, c] = sigmoid(sum_{ty, tx < 7} w7[0][ty][tx] avg[b, (jy + ty - 3, jx + tx - 3), c]
+ *                                         + w7[1][ty][tx] mx[b, (jy + ty - 3, jx + tx - 3), c])   (zero outside P x P)
+ *     xcnn[b, j, :] = g[b, j, :];   X0[b, 0, :] = cls + pos[0];   X0[b, 1 + j, :] = (xcnn[b, j, :] + pos[1 + j]) + pos[0]
+ *   e [3, B, NP, 64] is written for the backward.  The backward takes dX0 [B, T, 64] and dxcnn [B, NP, 64] (the CNN
+ *   classifier's path), recomputes avg / mx and the arg max (the first maximum in k order) from e, and writes dpa_k,
+ *   dpb_k and one partial row per sample,
+ *     part[b] = [dW_1 NP x n_1 | dbias_1 NP | dW_2 | dbias_2 | dW_3 | dbias_3 | dw7 98 | dxs1, dxs2]
+ *   (vc_glt_fuse_part_floats(P) floats); the caller sums the rows (vc_colsum) and takes dpos / dcls from dX0:
+ *   dpos[0] = sum over all B T rows, dpos[1 + j] = sum_b dX0[b, 1 + j], dcls = sum_b dX0[b, 0].
+ *
+ * vc_glt_upconv_fwd / _wgrad / _dgrad: nn.Upsample(scale_factor = s, nearest) followed by Conv2d(C, O, 3, padding 1)
+ *   as ONE implicit GEMM on v_mfma_f32_32x32x2_f32 (vc_conv3x3_tap_*'s structure: tap-major K, Wt from vc_conv3x3_pack
+ *   mode 0); the upsampled tensor is never written.  x [B P^2, ldx] rows of a P x P map, y / dy [B (sP)^2, ldy] rows,
+ *   s in {1, 2, 3}:
+ *     y[b, (i, j), o] = bias[o] + sum_{di, dj < 3} sum_c w[o][c][di][dj] u[b, (i + di - 1, j + dj - 1), c],
+ *     u[b, (p, q), c] = x[b, (floor(p / s), floor(q / s)), c] for 0 <= p, q < sP, 0 outside
+ *   wgrad: dw [O][C][3][3] (the torch layout) and db [O], both overwritten; dgrad: dx = beta dx + the sum over the
+ *   s x s replicas of each input pixel (K = s^2 x 9 taps x O walked in a fixed order).  Small grids split K into
+ *   slabs of ws (combined in slice order by a second launch); ws may be null.
+ *
+ * vc_glt_sigmse_fwd / _bwd: y [rows, C] (ldy) is overwritten by sigmoid(y) and
+ *     loss = (accumulate ? loss : 0) + weight / (rows C) * sum (sigmoid(y) - t)^2        (t [rows, C], ldt)
+ *   The per-block partial sums (2048 elements each) and their combination are FP64: every block writes its partial to
+ *   ws (vc_glt_sigmse_ws_floats(rows, C) floats, 8-B aligned), the last-arriving block (one zeroed arrival counter, left
+ *   zero) adds them in block order and rounds once to fp32.  bwd: d[r, c] = dloss * 2 weight / (rows C) *
+ *   (sg - t) sg (1 - sg) from the saved sigmoid sg (d may be sg).
+ *
+ * vc_glt_tail_fwd / _bwd: the classifier tail: avg[b, k] = mean_t z[b, t, k] over z [B, HW, 32] (ldz),
+ *     p2 = softmax(W2 avg + b2),  out = c1 lg1 + c2 p2      (raw logits plus probabilities; c1, c2 device scalars;
+ *   ncls <= 256).  bwd: dlg1, dz (lddz) and part[b] = [dW2 ncls x 32 | db2 ncls | dc1, dc2] (ncls * 33 + 2 floats). */
+VC_API int vc_glt_crops(int B, int C, int P, const float* x, float* r1, float* r2, float* r3, int ld,
+                        hipStream_t stream);
+VC_API int vc_glt_fuse_part_floats(int P);
+VC_API int vc_glt_fuse_fwd(int B, int P, const float* pa1, const float* pb1, const float* pa2, const float* pb2,
+                           const float* pa3, const float* pb3, const float* xs1, const float* xs2, const float* W1,
+                           const float* b1, const float* W2, const float* b2, const float* W3, const float* b3,
+                           const float* w7, const float* pos, const float* cls, float* xcnn, float* X0, float* e,
+                           hipStream_t stream);
+VC_API int vc_glt_fuse_bwd(int B, int P, const float* pa1, const float* pb1, const float* pa2, const float* pb2,
+                           const float* pa3, const float* pb3, const float* xs1, const float* xs2, const float* W1,
+                           const float* W2, const float* W3, const float* w7, const float* xcnn, const float* e,
+                           const float* dX0, const float* dxcnn, float* dpa1, float* dpb1, float* dpa2, float* dpb2,
+                           float* dpa3, float* dpb3, float* part, hipStream_t stream);
+VC_API int vc_glt_upconv_fwd(int B, int P, int s, int C, int O, const float* x, long ldx, const float* wt,
+                             const float* bias, float* y, long ldy, float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_glt_upconv_wgrad(int B, int P, int s, int C, int O, const float* x, long ldx, const float* dy, long lddy,
+                               float* dw, float* db, float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_glt_upconv_dgrad(int B, int P, int s, int C, int O, const float* dy, long lddy, const float* wt,
+                               float beta, float* dx, long lddx, float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_glt_sigmse_ws_floats(long rows, int C);
+VC_API int vc_glt_sigmse_fwd(long rows, int C, float* y, long ldy, const float* t, long ldt, float weight,
+                             int accumulate, float* loss, float* ws, long ws_floats, unsigned int* counter,
+                             hipStream_t stream);
+VC_API int vc_glt_sigmse_bwd(long rows, int C, const float* sg, long lds, const float* t, long ldt, float weight,
+                             const float* dloss, float* d, long ldd, hipStream_t stream);
+VC_API int vc_glt_tail_fwd(int B, int ncls, int HW, const float* lg1, const float* z, long ldz, const float* W2,
+                           const float* b2, const float* c1, const float* c2, float* p2, float* avg, float* out,
+                           hipStream_t stream);
+VC_API int vc_glt_tail_bwd(int B, int ncls, int HW, const float* dout, const float* lg1, const float* p2,
+                           const float* avg, const float* W2, const float* c1, const float* c2, float* dlg1, float* dz,
+                           long lddz, float* part, hipStream_t stream);
+
 #endif /* VITCNN_H */

@@ -121,6 +121,34 @@ class Cross_fusion_CNN_Loss(nn.Module):
         return _CrossFusionLossFn.apply(o1, o2, o3, target.to(device=o1.device, dtype=torch.int64).contiguous(), w)
 
 
+class GLT_Loss(nn.Module):
+    """The criterion of GLT-Net's training loop (the reference's utils.py:train_epoch adds the model's reconstruction
+    loss to the cross entropy): for output = (x_cls, con_loss), CrossEntropyLoss(weight)(x_cls, target) + con_loss.
+    On the device the cross entropy is `vc_ce_fwd` / `vc_ce_bwd` and the sum one scalar add, all on the current stream
+    (graph-capturable); on CPU tensors it is the formula itself in torch (host-side checks only: the model has no CPU
+    path)."""
+
+    def __init__(self, weight=None):
+        super().__init__()
+        self.ce = CrossEntropyLoss(weight=weight)
+
+    @property
+    def weight(self):
+        return self.ce.weight
+
+    def forward(self, output, target: torch.Tensor) -> torch.Tensor:
+        x_cls, con_loss = output
+        if con_loss.dim() != 0:
+            raise RuntimeError(f"expected (x_cls [B, C], con_loss []), got con_loss {list(con_loss.shape)}")
+        if x_cls.device.type != "cuda":
+            if x_cls.dim() != 2 or target.dim() != 1 or target.shape[0] != x_cls.shape[0]:
+                raise RuntimeError(f"expected logits [B, C] and target [B], got {list(x_cls.shape)} / {list(target.shape)}")
+            w = self.ce.weight
+            return nn.functional.cross_entropy(x_cls, target.to(torch.int64), weight=None if w is None else w.to(x_cls)) + \
+                con_loss
+        return self.ce(x_cls, target.to(x_cls.device)) + con_loss.to(torch.float32)
+
+
 class _EndNetLossFn(torch.autograd.Function):
     """loss and the three gradients in one launch (vc_endnet_loss_fwd_bwd); the gradients wait side by side in one
     buffer for the backward, which scales them by the incoming d(loss)"""

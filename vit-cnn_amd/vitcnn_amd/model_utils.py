@@ -16,7 +16,8 @@ Registered: "Multimodality_Mamba" (the README's "ViT-CNN (ours)"), "S2EFT" (conf
 `Cross_fusion_CNN_Loss` over its three outputs, and `val` / `test` read the first), and the per-pixel models
 "EndNet" (:119-128, `EndNet_Loss` over its five outputs) and "SpectralFormer" (:377-399), both with patch_size 1, and
 "HCTnet" (:351-363; the HSI cube reduced to 3 principal components, `PatchBatcher(applyPCA=True)`) and "MHST"
-(:314-335; patch_size 8, the one even patch side).
+(:314-335; patch_size 8), and "GLT_Net" (no branch in the reference's registry: this project's defaults, `_get_glt`;
+patch_size 24 = three times the model's 8, the three scales being centre crops of one window; `GLT_Loss`).
 The reference's other branches import modules absent from the reference tree (SURVEY.md section 2a
 row 22) and are out of scope for this path.
 
@@ -48,7 +49,7 @@ from .optim import AdamW
 from .window import SlidingWindowInference
 
 MDLRS = ("Early_fusion_CNN", "Middle_fusion_CNN", "Late_fusion_CNN", "Cross_fusion_CNN")
-REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT") + MDLRS + ("EndNet", "SpectralFormer", "HCTnet", "MHST")
+REGISTERED = ("Multimodality_Mamba", "S2EFT", "FusAtNet", "MFT") + MDLRS + ("EndNet", "SpectralFormer", "HCTnet", "MHST", "GLT_Net")
 
 
 def camel_to_snake(name: str) -> str:
@@ -89,6 +90,8 @@ def get_model(name, **kwargs):
         return _get_hctnet(n_bands, n_classes, device, kwargs)
     if name == "MHST":
         return _get_mhst(n_bands, n_bands2, n_classes, device, kwargs)
+    if name == "GLT_Net":
+        return _get_glt(n_bands, n_bands2, n_classes, device, kwargs)
     kwargs.setdefault("patch_size", 9)
     patch_size = kwargs["patch_size"]
     center_pixel = True
@@ -294,6 +297,39 @@ def _get_mhst(n_bands, n_bands2, n_classes, device, kwargs):
     optimizer = AdamW(model.parameters(), lr=lr)
     criterion = CrossEntropyLoss(weight=kwargs["weights"])
     kwargs.setdefault("epoch", 1000)
+    kwargs.setdefault("batch_size", 64)
+    kwargs.setdefault("supervision", "full")
+    kwargs["center_pixel"] = True
+    return model, optimizer, criterion, kwargs
+
+
+def _get_glt(n_bands, n_bands2, n_classes, device, kwargs):
+    """GLT-Net.  The reference's `get_model` has no branch for this model (its main.py lists it as unusable "for now"),
+    so these defaults are THIS PROJECT'S choice, taken from the shapes in the reference module's comments and from the
+    sibling transformers' branches: GLT(l1, l2, patch_size 8, num_patches 64, width 64 / decoder width 32, 5 + 5 layers
+    of 4 heads of 16, mlp_dim 8, dropout 0.1), Adam(lr 5e-4) as the fused AdamW with weight_decay 0, `GLT_Loss` (weighted
+    CE + the model's reconstruction loss), epoch 500, batch 64; under applyPCA the model is built for 30 bands.
+    kwargs["patch_size"] is what the batcher and `test()` cut: 24 = 3 * the model's patch side 8
+    (kwargs["glt_patch_size"]); a caller who passes patch_size passes the cut size, a multiple of 6."""
+    from .glt import GLT
+    from .losses import GLT_Loss
+    cut = kwargs.setdefault("patch_size", 24)
+    if cut % 6 or cut < 6:
+        raise ValueError(f"GLT_Net: patch_size is the 3P window the batcher cuts and must be a multiple of 6, got {cut}")
+    p = kwargs.setdefault("glt_patch_size", cut // 3)
+    if 3 * p != cut:
+        raise ValueError(f"GLT_Net: glt_patch_size {p} is not patch_size {cut} / 3")
+    kwargs.setdefault("applyPCA", False)
+    if kwargs["applyPCA"]:
+        n_bands = 30
+        kwargs.setdefault("pca_components", 30)   # what PatchBatcher / test() must reduce the cube to (pca.py)
+    model = GLT(l1=n_bands, l2=n_bands2, patch_size=p, num_patches=p * p, num_classes=n_classes, encoder_embed_dim=64,
+                decoder_embed_dim=32, en_depth=5, en_heads=4, de_depth=5, de_heads=4, mlp_dim=8, dim_head=16, dropout=0.1,
+                emb_dropout=0.1).to(device)
+    lr = kwargs.setdefault("lr", 0.0005)
+    optimizer = AdamW(model.parameters(), lr=lr, weight_decay=0.0)
+    criterion = GLT_Loss(weight=kwargs["weights"])
+    kwargs.setdefault("epoch", 500)
     kwargs.setdefault("batch_size", 64)
     kwargs.setdefault("supervision", "full")
     kwargs["center_pixel"] = True

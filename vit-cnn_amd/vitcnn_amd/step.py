@@ -18,7 +18,7 @@ import torch
 
 from . import parallel, seeds
 from .flat import FlatParams, expose_grad_views
-from .losses import Cross_fusion_CNN_Loss, CrossEntropyLoss, EndNet_Loss, ce_forward_backward
+from .losses import Cross_fusion_CNN_Loss, CrossEntropyLoss, EndNet_Loss, GLT_Loss, ce_forward_backward
 from .model import Multimodality_Mamba, _Program
 from .optim import AdamW
 from .program import counters
@@ -90,7 +90,7 @@ def _capture_step_blocker(net, optimizer, criterion):
         return "the model's forward does not take two inputs"
     if not isinstance(optimizer, AdamW) or optimizer._owner() is not net:
         return "the optimizer is not the package's fused AdamW / Adam over this model"
-    if not isinstance(criterion, (CrossEntropyLoss, Cross_fusion_CNN_Loss, EndNet_Loss)):
+    if not isinstance(criterion, (CrossEntropyLoss, Cross_fusion_CNN_Loss, EndNet_Loss, GLT_Loss)):
         return "the criterion is not one of the package's losses"
     return None
 
