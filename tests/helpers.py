@@ -1,5 +1,6 @@
 """Shared test helpers: hash-filled state dicts keyed by the reference's 1704 state_dict names."""
 import contextlib
+import glob
 import json
 import os
 
@@ -73,6 +74,67 @@ def program_spy(model_cls=None):
         yield progs
     finally:
         ProgramFunction.forward = staticmethod(orig)
+
+
+@contextlib.contextmanager
+def launch_trace(L):
+    """Every call of a `vc_*` entry point of the bound library `L` inside the block, in order, as [name, [the
+    non-pointer arguments]]: the integer and floating-point arguments by `L.sigs[name]`, every `c_void_p` (buffers,
+    the stream) dropped.  What a model's program asks of the library, free of addresses (tests/golden/
+    launch_trace.json)."""
+    import ctypes
+    trace, orig = [], {}
+
+    def wrap(name, fn):
+        kinds = [None if t is ctypes.c_void_p else float if t in (ctypes.c_float, ctypes.c_double) else int
+                 for t in L.sigs[name]]
+
+        def call(*args):
+            trace.append([name, [k(a) for k, a in zip(kinds, args) if k is not None]])
+            return fn(*args)
+
+        return call
+
+    for name in L.sigs:
+        orig[name] = getattr(L, name)
+        setattr(L, name, wrap(name, orig[name]))
+    try:
+        yield trace
+    finally:
+        for name, fn in orig.items():
+            setattr(L, name, fn)
+
+
+def load_case(name, cache):
+    """A comparison model's fixture (tests/golden/<name>.npz and its <name>_p*.npz / <name>_g*.npz parts): {"keys",
+    "state" (initial state_dict, fp32), "grads" (the float64 twin's), "running" (BatchNorm running statistics and
+    num_batches_tracked after the training forward), and the scalars / arrays of <name>.npz as tensors}; loaded once
+    into `cache`"""
+    if name not in cache:
+        z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+        d = {k: torch.from_numpy(np.asarray(z[k])) for k in z.files if k != "keys" and not k.startswith("r:")}
+        d["keys"] = [str(k) for k in z["keys"]]
+        d["running"] = {k[2:]: torch.from_numpy(np.asarray(z[k])) for k in z.files if k.startswith("r:")}
+        for tag, field in (("p", "state"), ("g", "grads")):
+            d[field] = {}
+            for path in sorted(glob.glob(os.path.join(GOLDEN, f"{name}_{tag}[0-9].npz"))):
+                zz = np.load(path, allow_pickle=False)
+                d[field].update({k[2:]: torch.from_numpy(np.asarray(zz[k])) for k in zz.files})
+        assert list(d["state"]) == d["keys"]
+        cache[name] = d
+    return cache[name]
+
+
+def grad_rule_fraction(got, want):
+    """the worst |g - g_ref| / (1e-3 |g_ref| + 1e-5 gmax) over all parameters (norms per tensor), and its key"""
+    gmax = max(float(v.double().norm()) for v in want.values())
+    worst, where = 0.0, None
+    for k, w in want.items():
+        w = w.double()
+        f = float((got[k].double().cpu().reshape(w.shape) - w).norm()) / (1e-3 * float(w.norm()) + 1e-5 * gmax)
+        if f > worst:
+            worst, where = f, k
+    return worst, where
 
 
 def cpu_masks(prog):

@@ -1,11 +1,7 @@
 """The MHST fixtures (tests/golden/gen_mhst_golden.py) and the model each was made with, shared by tests/test_mhst*.py."""
-import glob
-import os
-
-import numpy as np
 import torch
 
-from helpers import GOLDEN
+from helpers import grad_rule_fraction, load_case  # noqa: F401  (grad_rule_fraction: the tests import it from here)
 
 REGISTRY = dict(patch_size=8, num_patches=64, encoder_embed_dim=64, en_heads=4, mlp_dim=8, dropout=0.1, emb_dropout=0.1,
                 coefficient_hsi=0.6, coefficient_vit=0.7, hsp_vit_num_heads=16, head_tau=5, use_head_select=True,
@@ -18,21 +14,8 @@ _CACHE = {}
 
 
 def load(name):
-    """{"keys", "state" (initial state_dict, fp32), "grads" (float64 twin's, fp32), "running", and the scalars / arrays
-    of <name>.npz as tensors}; loaded once"""
-    if name not in _CACHE:
-        z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
-        d = {k: torch.from_numpy(np.asarray(z[k])) for k in z.files if k != "keys" and not k.startswith("r:")}
-        d["keys"] = [str(k) for k in z["keys"]]
-        d["running"] = {k[2:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("r:")}
-        for tag, field in (("p", "state"), ("g", "grads")):
-            d[field] = {}
-            for path in sorted(glob.glob(os.path.join(GOLDEN, f"{name}_{tag}[0-9].npz"))):
-                zz = np.load(path, allow_pickle=False)
-                d[field].update({k[2:]: torch.from_numpy(zz[k]) for k in zz.files})
-        assert list(d["state"]) == d["keys"]
-        _CACHE[name] = d
-    return _CACHE[name]
+    """the fixture `name` (helpers.load_case), loaded once"""
+    return load_case(name, _CACHE)
 
 
 def build(name, p_zero=True):
@@ -45,15 +28,3 @@ def build(name, p_zero=True):
             if isinstance(mod, torch.nn.Dropout):
                 mod.p = 0.0
     return m.train()
-
-
-def grad_rule_fraction(got, want):
-    """the worst |g - g_ref| / (1e-3 |g_ref| + 1e-5 gmax) over all parameters (norms per tensor), and its key"""
-    gmax = max(float(v.double().norm()) for v in want.values())
-    worst, where = 0.0, None
-    for k, w in want.items():
-        w = w.double()
-        f = float((got[k].double().cpu().reshape(w.shape) - w).norm()) / (1e-3 * float(w.norm()) + 1e-5 * gmax)
-        if f > worst:
-            worst, where = f, k
-    return worst, where

@@ -1,13 +1,18 @@
 """The comparison models' shared autograd bridge and counter pool (vitcnn_amd/program.py): a
 backward through one output of a multi-output model equals the backward with explicit zero gradients for the others, a
 forward under no_grad keeps no program and leaves the next training step alone, and the arrival counters are one array
-per (device, stream).  Smallest shapes the models accept: every check here is about the bridge, not the kernels."""
+per (device, stream).  Smallest shapes the models accept: every check here is about the bridge, not the kernels.
+
+The launch sequence of the models built from `Program`'s shared helpers is pinned: one training forward + backward asks
+the library for exactly the recorded calls (entry point and non-pointer arguments, in order; tests/launch_cases.py), so a
+refactor of the shared host code that moves a launch, an argument or the workspace's size fails here."""
 import gc
 import weakref
 
 import pytest
 import torch
 
+import launch_cases
 from helpers import program_spy
 
 pytestmark = pytest.mark.gpu
@@ -87,3 +92,13 @@ def test_counter_pool_is_one_array_per_device_and_stream():
     assert a != 0 and counters(dev, cur) == a
     b = counters(dev, other.cuda_stream)
     assert b not in (0, a) and counters(dev, other.cuda_stream) == b
+
+
+@pytest.mark.parametrize("case", list(launch_cases.CASES))
+def test_launch_sequence_is_the_recorded_one(case):
+    _need_gpu()
+    want = launch_cases.fixture()[case]
+    got = launch_cases.record(case)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (case, i, g, w)     # the first call that differs
+    assert want and got == want

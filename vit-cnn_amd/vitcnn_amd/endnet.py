@@ -25,7 +25,6 @@ import torch.nn as nn
 from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
-from .model import N_COUNTERS
 
 FILTERS = (16, 32, 64, 128)
 C_MAX, NCLS_MAX = 512, 64           # bands per modality (the fused layer's K bound), classes
@@ -147,8 +146,7 @@ class _Program(program.Program):
                                dz.data_ptr() if dz is not None else None, N, G[name + ".weight"], G[name + ".bias"],
                                G[bn + ".weight"] if isbn else None, G[bn + ".bias"] if isbn else None, self.s)
         if dx is not None:
-            self.L.vc_gemm_ex(0, 0, B, K, N, 1.0, dz.data_ptr(), N, 0, P[name + ".weight"], K, 0, beta, dx, lddx, 0, 1,
-                              None, None, 0, 0, 0, None, self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
+            self.gemm(0, 0, B, K, N, dz.data_ptr(), N, P[name + ".weight"], K, dx, lddx, beta=beta)
 
     # ------------------------------------------------------------ forward
     def _forward(self):

@@ -264,10 +264,6 @@ class _Program(program.Program):
         self.no_grad_ids.add(id(y))
         return y
 
-    def gemm(self, tA, tB, M, N, K, A, lda, Bm, ldb, beta, C, ldc, bias=None, bias_grad=None):
-        self.L.vc_gemm_ex(tA, tB, M, N, K, 1.0, A, lda, 0, Bm, ldb, 0, beta, C, ldc, 0, 1, bias, None, 0, 0, 0,
-                          bias_grad, self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
-
     def conv3(self, x, ldx, H, C, conv, pad):
         """x [B,H,W,C] rows (ld ldx) -> conv3x3 + bias, [B,OH,OH,O] contiguous.
 
@@ -297,7 +293,7 @@ class _Program(program.Program):
         else:
             col = self.new(M, K)
             L.vc_im2col3x3_pad(B, H, H, C, pad, x.data_ptr(), ldx, col.data_ptr(), self.s)
-            self.gemm(0, 1, M, O, K, col.data_ptr(), K, conv.weight.data_ptr(), K, 0.0, y.data_ptr(), O,
+            self.gemm(0, 1, M, O, K, col.data_ptr(), K, conv.weight.data_ptr(), K, y.data_ptr(), O,
                       bias=conv.bias.data_ptr())
             del col
 
@@ -321,12 +317,12 @@ class _Program(program.Program):
                 return
             colr = self.new(M, K)   # recomputed: cheaper than keeping every im2col matrix
             L.vc_im2col3x3_pad(B, H, H, C, pad, x.data_ptr(), ldx, colr.data_ptr(), self.s)
-            self.gemm(1, 0, O, K, M, dy.data_ptr(), O, colr.data_ptr(), K, 0.0, self.pgrad(conv.weight), K,
+            self.gemm(1, 0, O, K, M, dy.data_ptr(), O, colr.data_ptr(), K, self.pgrad(conv.weight), K,
                       bias_grad=self.pgrad(conv.bias))
             if id(x) in self.no_grad_ids:
                 return
             dcol = colr
-            self.gemm(0, 0, M, K, O, dy.data_ptr(), O, conv.weight.data_ptr(), K, 0.0, dcol.data_ptr(), K)
+            self.gemm(0, 0, M, K, O, dy.data_ptr(), O, conv.weight.data_ptr(), K, dcol.data_ptr(), K)
             L.vc_col2im3x3_pad(B, H, H, C, pad, dcol.data_ptr(), self.grad_of(x).data_ptr(), ldx, 1, self.s)
 
         self.record(bwd, x, y) if wt is None else self.record(bwd, x, y, wt)
@@ -509,7 +505,7 @@ class _Program(program.Program):
         Mo = B * H * H
         logits = self.new(Mo, m.ncls)
         conv6 = m.cm.conv6
-        self.gemm(0, 1, Mo, m.ncls, C, x.data_ptr(), C, conv6.weight.data_ptr(), C, 0.0, logits.data_ptr(), m.ncls,
+        self.gemm(0, 1, Mo, m.ncls, C, x.data_ptr(), C, conv6.weight.data_ptr(), C, logits.data_ptr(), m.ncls,
                   bias=conv6.bias.data_ptr())
         self.head = (x, Mo, C)
         if H == 1:
@@ -527,10 +523,11 @@ class _Program(program.Program):
         self.gflat = self.new(m._n_params)
         self.L.vc_fill(m._n_params, self.gflat.data_ptr(), 0.0, self.s)
         conv6 = m.cm.conv6
-        self.gemm(1, 0, m.ncls, C, Mo, dlogits.data_ptr(), m.ncls, x.data_ptr(), C, 0.0, self.pgrad(conv6.weight), C,
+        self.gemm(1, 0, m.ncls, C, Mo, dlogits.data_ptr(), m.ncls, x.data_ptr(), C, self.pgrad(conv6.weight), C,
                   bias_grad=self.pgrad(conv6.bias))
         gx, beta = self.acc(x)
-        self.gemm(0, 0, Mo, C, m.ncls, dlogits.data_ptr(), m.ncls, conv6.weight.data_ptr(), C, beta, gx.data_ptr(), C)
+        self.gemm(0, 0, Mo, C, m.ncls, dlogits.data_ptr(), m.ncls, conv6.weight.data_ptr(), C, gx.data_ptr(), C,
+                  beta=beta)
         for fn in reversed(self.tape):
             fn()
         self.tape, self.g, self.keep = [], {}, {}

@@ -36,11 +36,10 @@ import torch.nn as nn
 from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
-from .model import N_COUNTERS
 
 LN_EPS = 1e-5
 DIM = 64            # encoder width = the channels of seq2img(x_cnn) = decoder_pred1's outputs
-HEADS, DIM_HEAD = 4, 16
+HEADS, DIM_HEAD = program.ATTN_HEADS, program.ATTN_DIM_HEAD
 P_MAX = 8           # vc_glt_fuse_*: the sample's fused maps in LDS
 NCLS_MAX = 256      # vc_glt_tail_*
 
@@ -224,12 +223,6 @@ class _Program(program.Program):
         self.seed_dropout(self.train)
 
     # ------------------------------------------------------------ helpers
-    def p(self, mod):
-        return float(mod.p) if self.train else 0.0
-
-    def bytes(self, *shape):
-        return torch.empty(*shape, dtype=torch.uint8, device=self.dev)
-
     def count_batches(self):
         """the shared conv1 / conv2 BatchNorms ran three times: num_batches_tracked += 3, each tensor once per launch"""
         seen = {}
@@ -238,82 +231,15 @@ class _Program(program.Program):
         for n in sorted({c for _, c in seen.values()}):
             torch._foreach_add_([t for t, c in seen.values() if c == n], n)
 
-    def gemm(self, tA, tB, M, N, K, A, lda, Bm, ldb, C, ldc, beta=0.0, bias=None, bias_grad=None, addend=None, add_ld=0,
-             add_mod=0):
-        self.L.vc_gemm_ex(tA, tB, M, N, K, 1.0, A, lda, 0, Bm, ldb, 0, beta, C, ldc, 0, 1, bias, addend, add_ld, add_mod,
-                          0, bias_grad, self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
-
-    def linear(self, x, M, K, N, pfx, bias=True, ldx=None, **kw):
-        y = self.new(M, N)
-        self.gemm(0, 1, M, N, K, x if isinstance(x, int) else x.data_ptr(), ldx or K, self.P[pfx + ".weight"], K,
-                  y.data_ptr(), N, bias=self.P[pfx + ".bias"] if bias else None, **kw)
-        return y
-
-    def linear_bwd(self, dy, x, M, K, N, pfx, bias=True, dx=None, lddx=None, beta=0.0, ldx=None):
-        """dW (+ db) of y = x W^T + b into the flat gradient; dx (new, or beta dx + ... at the pointer given)"""
-        self.gemm(1, 0, N, K, M, dy.data_ptr(), N, x if isinstance(x, int) else x.data_ptr(), ldx or K,
-                  self.G[pfx + ".weight"], K, bias_grad=self.G[pfx + ".bias"] if bias else None)
-        out = None
-        if dx is None:
-            out = self.new(M, K)
-            dx, lddx = out.data_ptr(), K
-        self.gemm(0, 0, M, K, N, dy.data_ptr(), N, self.P[pfx + ".weight"], K, dx, lddx, beta=beta)
-        return out
-
-    def lnorm(self, pfx, X, R, ldx, D):
-        Y, mu, rs = self.new(R, D), self.new(R), self.new(R)
-        self.L.vc_layernorm_fwd(R, D, X, ldx, self.P[pfx + ".weight"], self.P[pfx + ".bias"], LN_EPS, Y.data_ptr(), D,
-                                mu.data_ptr(), rs.data_ptr(), self.s)
-        return Y, mu, rs
-
-    def ln_bwd(self, pfx, dY, X, ldx, mu, rs, R, D, dx, lddx, beta):
-        self.L.vc_layernorm_bwd(R, D, dY.data_ptr(), D, X, ldx, self.P[pfx + ".weight"], mu.data_ptr(), rs.data_ptr(),
-                                dx, lddx, beta, self.G[pfx + ".weight"], self.G[pfx + ".bias"], 0.0, self.scr.data_ptr(),
-                                self.SCRATCH, self.s)
-
-    def dropped(self, site, x, add, n, p, D):
-        """add + dropout_p(x) as a new tensor (x + add, or x itself, at p = 0)"""
-        if p > 0:
-            y = torch.empty_like(x)
-            self.drop(site, x, add, y, n, p)
-            return y
-        if add is None:
-            return x
-        y = torch.empty_like(x)
-        self.L.vc_add2_2d(n // D, D, x.data_ptr(), D, add.data_ptr(), D, y.data_ptr(), D, 0.0, self.s)
-        return y
-
-    def drop_bwd(self, site, dy, n, p):
-        if p <= 0:
-            return dy
-        dx = torch.empty_like(dy)
-        self.L.vc_dropout_bwd(n, dy.data_ptr(), self.masks[site].data_ptr(), p, dx.data_ptr(), self.s)
-        return dx
-
-    def bn_bwd(self, pfx, dz, y, mean, inv, M, C, beta_w=0.0):
-        dy = self.new(M, C)
-        self.L.vc_bn_bwd_relu_ex(1 if self.train else 0, M, C, dz.data_ptr(), C, y.data_ptr(), C, mean.data_ptr(),
-                                 inv.data_ptr(), self.P[pfx + ".weight"], self.P[pfx + ".bias"], dy.data_ptr(), C, 0.0,
-                                 self.G[pfx + ".weight"], self.G[pfx + ".bias"], beta_w, self.scr.data_ptr(),
-                                 self.SCRATCH, self.cnt, N_COUNTERS, self.s)
-        return dy
-
-    def pack(self, name, O, C):
-        """the conv's weights tap-major, Wt [O][9][C rounded up to 4] (repacked per forward: the parameters move)"""
-        wt = self.new(O * 9 * ((C + 3) // 4 * 4))
-        self.L.vc_conv3x3_pack(O, C, 0, self.P[name], wt.data_ptr(), 0.0, self.s)
-        return wt
+    def transformer(self, tag, D):
+        """`{tag}_transformer` (GLT_Net.py:287-307), of width D over the T tokens, as program.encoder_fwd / _bwd take it"""
+        return dict(prefix=f"{tag}_transformer", T=self.T, D=D, hidden=self.m.mlp_dim, ff="net", site=tag)
 
     def conv(self, S, C, O, x, ldx, wt, bias):
         y = self.new(self.B * S * S, O)
         self.L.vc_conv3x3_tap_fwd(self.B, S, S, C, O, 1, x.data_ptr(), ldx, wt.data_ptr(), self.P[bias], y.data_ptr(), O,
                                   self.scr.data_ptr(), self.SCRATCH, self.s)
         return y
-
-    def reduce_part(self, part, width, col, n, out):
-        """out[0:n] = sum over the samples of part[b][col : col + n] (fixed order)"""
-        self.L.vc_colsum(self.B, n, part.data_ptr() + F32 * col, width, out, 0.0, self.scr.data_ptr(), self.SCRATCH,
-                         self.s)
 
     # ------------------------------------------------------------ forward
     def _forward(self):
@@ -333,14 +259,14 @@ class _Program(program.Program):
         pooled, sv["enc"] = [[None] * 3, [None] * 3], [[None] * 3, [None] * 3]
         for mi, (r, ld, C) in enumerate(rows):
             name = f"cnn_encoder.conv{mi + 1}"
-            wt0 = self.pack(name + ".0.weight", 32, C)
+            wt0 = self.pack3x3(name + ".0.weight", 32, C)
             for k in range(3):
                 S = (k + 1) * Pn
                 M = B * S * S
                 y = self.conv(S, C, 32, r[k], ld, wt0, name + ".0.bias")
                 z, mean, inv = self.bn(name + ".1", getattr(enc, f"conv{mi + 1}")[1], y, M, 32)
                 nk = f"{name}_{k + 1}"
-                wt1 = self.pack(nk + ".0.weight", 64, 32)
+                wt1 = self.pack3x3(nk + ".0.weight", 64, 32)
                 y2 = self.conv(S, 32, 64, z, 32, wt1, nk + ".0.bias")
                 z2, mean2, inv2 = self.bn(nk + ".1", getattr(enc, f"conv{mi + 1}_{k + 1}")[1], y2, M, 64)
                 pl, arg = self.new(M // 4, 64), self.bytes(M // 4, 64)
@@ -356,15 +282,15 @@ class _Program(program.Program):
                           P["encoder_embedding2.bias"], P["encoder_embedding3.weight"], P["encoder_embedding3.bias"],
                           P["sa_gdr.conv.weight"], P["encoder_pos_embed"], P["cls_token"], xcnn.data_ptr(),
                           X0.data_ptr(), e.data_ptr(), s)
-        self.pe = self.p(m.dropout)
+        self.pe = self.drop_p(m.dropout)
         X = self.dropped("emb", X0, None, B * T * DIM, self.pe, DIM)
         sv.update(pooled=pooled, xcnn=xcnn, e=e)
         self.lay = {}
-        X = self.layers_fwd("en", m.en_transformer, m.en_depth, X, DIM)
+        X, self.lay["en"] = self.encoder_fwd(X, layers=m.en_transformer.layers, **self.transformer("en", DIM))
         # decoder (:387-415): embedding + position rows, the width-32 transformer, the prediction back to 64 channels
         R, Dd = B * T, m.de_dim
-        D0 = self.linear(X, R, DIM, Dd, "decoder_embedding", addend=P["decoder_pos_embed"], add_ld=Dd, add_mod=T)
-        Dl = self.layers_fwd("de", m.de_transformer, m.de_depth, D0, Dd)
+        D0 = self.linear(X, R, DIM, Dd, "decoder_embedding", add=P["decoder_pos_embed"], add_ld=Dd, add_mod=T)
+        Dl, self.lay["de"] = self.encoder_fwd(D0, layers=m.de_transformer.layers, **self.transformer("de", Dd))
         Yp = self.linear(Dl, R, Dd, DIM, "decoder_pred1")
         xcon = self.new(B * NP, DIM)     # the token rows without cls = the [B, 64, P, P] map, channels-last
         L.vc_add2_2d(B, NP * DIM, Yp.data_ptr() + F32 * DIM, T * DIM, None, 0, xcon.data_ptr(), NP * DIM, 0.0, s)
@@ -373,7 +299,7 @@ class _Program(program.Program):
         for i in range(6):
             sc, (r, ld, C) = i // 2 + 1, rows[i % 2]
             nm = f"cnn_decoder.dconv{i + 1}.{0 if sc == 1 else 1}"
-            wt = self.pack(nm + ".weight", C, DIM)
+            wt = self.pack3x3(nm + ".weight", C, DIM)
             n = B * (sc * Pn) ** 2
             y = self.new(n, ld)
             L.vc_glt_upconv_fwd(B, Pn, sc, DIM, C, xcon.data_ptr(), DIM, wt.data_ptr(), P[nm + ".bias"], y.data_ptr(), ld,
@@ -383,7 +309,7 @@ class _Program(program.Program):
                                 con.data_ptr(), self.scr.data_ptr(), self.SCRATCH, self.cnt, s)
             dec.append((nm, sc, C, ld, wt, y, r[sc - 1]))
         # classifier (:373-385): mlp_head on the cls row, the CNN classifier on the position-free x_cnn
-        Yc, muc, rsc = self.lnorm("mlp_head.0", X.data_ptr(), B, T * DIM, DIM)
+        Yc, muc, rsc = self.ln("mlp_head.0", X.data_ptr(), B, T * DIM, DIM)
         lg1 = self.linear(Yc, B, DIM, m.ncls, "mlp_head.1")
         yc = self.linear(xcnn, B * NP, DIM, 32, "cnn_classifier.conv1.0")
         zc, meanc, invc = self.bn("cnn_classifier.conv1.1", m.cnn_classifier.conv1[1], yc, B * NP, 32)
@@ -395,33 +321,6 @@ class _Program(program.Program):
         sv.update(Xlast=X, Dl=Dl, xcon=xcon, dec=dec, Yc=Yc, muc=muc, rsc=rsc, lg1=lg1, yc=yc, meanc=meanc, invc=invc,
                   p2=p2, avg=avg)
         return out, con
-
-    def layers_fwd(self, tag, tr, depth, X, D):
-        """a `Transformer` (GLT_Net.py:287-307) of width D: pre-norm layers of 4 heads of 16 over the T tokens"""
-        m, L, B, T = self.m, self.L, self.B, self.T
-        R, E, Hd = B * T, HEADS * DIM_HEAD, m.mlp_dim
-        self.lay[tag] = []
-        for li in range(depth):
-            pre = f"{tag}_transformer.layers.{li}"
-            att, ff = tr.layers[li][0].fn.fn, tr.layers[li][1].fn.fn
-            pa, p1, p2 = self.p(att.to_out[1]), self.p(ff.net[2]), self.p(ff.net[4])
-            Y, mu, rs = self.lnorm(pre + ".0.fn.norm", X.data_ptr(), R, D, D)
-            qkv = self.linear(Y, R, D, 3 * E, pre + ".0.fn.fn.to_qkv", bias=False)
-            O, lse = self.new(R, E), self.new(B, HEADS, T)
-            L.vc_s2eft_attn_fwd(B, T, HEADS, qkv.data_ptr(), DIM_HEAD ** -0.5, O.data_ptr(), lse.data_ptr(), self.s)
-            A2 = self.linear(O, R, E, D, pre + ".0.fn.fn.to_out.0")
-            X2 = self.dropped(f"{tag}{li}.attn", A2, X, R * D, pa, D)
-            Y2, mu2, rs2 = self.lnorm(pre + ".1.fn.norm", X2.data_ptr(), R, D, D)
-            H1 = self.linear(Y2, R, D, Hd, pre + ".1.fn.fn.net.0")
-            Gl = self.new(R, Hd)
-            L.vc_gelu_fwd(R * Hd, H1.data_ptr(), Gl.data_ptr(), self.s)
-            Gd = self.dropped(f"{tag}{li}.ff1", Gl, None, R * Hd, p1, Hd)
-            F2 = self.linear(Gd, R, Hd, D, pre + ".1.fn.fn.net.3")
-            X3 = self.dropped(f"{tag}{li}.ff2", F2, X2, R * D, p2, D)
-            self.lay[tag].append(dict(X=X, Y=Y, mu=mu, rs=rs, qkv=qkv, O=O, lse=lse, X2=X2, Y2=Y2, mu2=mu2, rs2=rs2,
-                                      H1=H1, Gd=Gd, pa=pa, p1=p1, p2=p2))
-            X = X3
-        return X
 
     # ------------------------------------------------------------ backward
     def backward(self, dout, dcon):
@@ -466,10 +365,10 @@ class _Program(program.Program):
         L.vc_fill_2d(B, DIM, dYp.data_ptr(), T * DIM, 0.0, s)
         L.vc_add2_2d(B, NP * DIM, dxcon.data_ptr(), NP * DIM, None, 0, dYp.data_ptr() + F32 * DIM, T * DIM, 0.0, s)
         dD = self.linear_bwd(dYp, sv["Dl"], R, Dd, DIM, "decoder_pred1")
-        dD = self.layers_bwd("de", m.de_depth, dD, Dd)
+        dD = self.encoder_bwd(dD, self.lay["de"], **self.transformer("de", Dd))
         L.vc_colsum(B, T * Dd, dD.data_ptr(), T * Dd, G["decoder_pos_embed"], 0.0, scr, ns, s)
         self.linear_bwd(dD, sv["Xlast"], R, DIM, Dd, "decoder_embedding", dx=dX.data_ptr(), lddx=DIM, beta=1.0)
-        dX = self.layers_bwd("en", m.en_depth, dX, DIM)
+        dX = self.encoder_bwd(dX, self.lay["en"], **self.transformer("en", DIM))
         # tokens, SA-GDR, the spatial embeddings and the fusion
         dX0 = self.drop_bwd("emb", dX, R * DIM, self.pe)
         pa, pb = sv["pooled"]
@@ -525,30 +424,3 @@ class _Program(program.Program):
                     L.vc_add2_2d(1, 32, tmp.data_ptr() + F32 * nw, 32, None, 0, G[name + ".0.bias"], 32, 1.0, s)
         self.sv, self.lay = {}, {}
         return grad
-
-    def layers_bwd(self, tag, depth, dX, D):
-        m, L, B, T = self.m, self.L, self.B, self.T
-        R, E, Hd = B * T, HEADS * DIM_HEAD, m.mlp_dim
-        for li in reversed(range(depth)):
-            pre = f"{tag}_transformer.layers.{li}"
-            st = self.lay[tag][li]
-            dF2 = self.drop_bwd(f"{tag}{li}.ff2", dX, R * D, st["p2"])
-            dGd = self.linear_bwd(dF2, st["Gd"], R, Hd, D, pre + ".1.fn.fn.net.3")
-            dGl = self.drop_bwd(f"{tag}{li}.ff1", dGd, R * Hd, st["p1"])
-            dH1 = self.new(R, Hd)
-            L.vc_gelu_bwd(R * Hd, dGl.data_ptr(), st["H1"].data_ptr(), dH1.data_ptr(), self.s)
-            dY2 = self.linear_bwd(dH1, st["Y2"], R, D, Hd, pre + ".1.fn.fn.net.0")
-            dX2 = self.new(R, D)
-            L.vc_add2_2d(R, D, dX.data_ptr(), D, None, 0, dX2.data_ptr(), D, 0.0, self.s)
-            self.ln_bwd(pre + ".1.fn.norm", dY2, st["X2"].data_ptr(), D, st["mu2"], st["rs2"], R, D, dX2.data_ptr(), D, 1.0)
-            dA2 = self.drop_bwd(f"{tag}{li}.attn", dX2, R * D, st["pa"])
-            dO = self.linear_bwd(dA2, st["O"], R, E, D, pre + ".0.fn.fn.to_out.0")
-            dqkv = self.new(R, 3 * E)
-            L.vc_s2eft_attn_bwd(B, T, HEADS, st["qkv"].data_ptr(), st["O"].data_ptr(), dO.data_ptr(),
-                                st["lse"].data_ptr(), DIM_HEAD ** -0.5, dqkv.data_ptr(), self.s)
-            dY = self.linear_bwd(dqkv, st["Y"], R, D, 3 * E, pre + ".0.fn.fn.to_qkv", bias=False)
-            dXi = self.new(R, D)
-            L.vc_add2_2d(R, D, dX2.data_ptr(), D, None, 0, dXi.data_ptr(), D, 0.0, self.s)
-            self.ln_bwd(pre + ".0.fn.norm", dY, st["X"].data_ptr(), D, st["mu"], st["rs"], R, D, dXi.data_ptr(), D, 1.0)
-            dX = dXi
-        return dX

@@ -277,18 +277,10 @@ class _Program(program.Program):
     def site_seed(self, k):
         return (self.seed + 1000003 * k) % (1 << 63)
 
-    def bytes(self, *shape):
-        return torch.empty(*shape, dtype=torch.uint8, device=self.dev)
-
-    def gemm(self, tA, tB, M, N, K, A, lda, Bm, ldb, C, ldc, bias=None, bias_grad=None):
-        self.L.vc_gemm_ex(tA, tB, M, N, K, 1.0, A, lda, 0, Bm, ldb, 0, 0.0, C, ldc, 0, 1, bias, None, 0, 0, 0,
-                          bias_grad, self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
-
     def conv(self, pfx, x, ldx, H, C, O):
         """valid 3x3 conv of channels-last rows x [B, H, H, C] (ld ldx) -> (y [B (H-2)^2, O], the tap-major weight)"""
         L, B = self.L, self.B
-        wt = self.new(O * 9 * ((C + 3) // 4 * 4))
-        L.vc_conv3x3_pack(O, C, 0, self.P[pfx + ".weight"], wt.data_ptr(), 0.0, self.s)
+        wt = self.pack3x3(pfx + ".weight", O, C)
         y = self.new(B * (H - 2) * (H - 2), O)
         L.vc_conv3x3_tap_fwd(B, H, H, C, O, 0, x.data_ptr(), ldx, wt.data_ptr(), self.P[pfx + ".bias"], y.data_ptr(), O,
                              self.scr.data_ptr(), self.SCRATCH, self.s)

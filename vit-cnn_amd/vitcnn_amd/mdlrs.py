@@ -168,10 +168,6 @@ class _Program(program.Program):
         return [torch.stack(ds)]
 
     # ------------------------------------------------------------ primitives
-    def gemm(self, tA, tB, M, N, K, A, lda, Bm, ldb, C, ldc, bias=None, bias_grad=None, beta=0.0):
-        self.L.vc_gemm_ex(tA, tB, M, N, K, 1.0, A, lda, 0, Bm, ldb, 0, beta, C, ldc, 0, 1, bias, None, 0, 0, 0,
-                          bias_grad, self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
-
     def conv1x1(self, name, x, M, K, N):
         """y [M, N] = x [M, K] W^T + bias"""
         y = self.new(M, N)
@@ -185,8 +181,7 @@ class _Program(program.Program):
             self.gemm(0, 0, M, K, N, dy, N, self.P[name + ".weight"], K, dx, K, beta=beta)
 
     def conv3x3(self, name, x, ldx, H, C, O):
-        wt = self.new(O * 9 * ((C + 3) // 4 * 4))
-        self.L.vc_conv3x3_pack(O, C, 0, self.P[name + ".weight"], wt.data_ptr(), 0.0, self.s)
+        wt = self.pack3x3(name + ".weight", O, C)
         y = self.new(self.B * H * H, O)
         self.L.vc_conv3x3_tap_fwd(self.B, H, H, C, O, 1, x, ldx, wt.data_ptr(), self.P[name + ".bias"], y.data_ptr(), O,
                                   self.scr.data_ptr(), self.SCRATCH, self.s)

@@ -172,10 +172,6 @@ class _Program(program.Program):
         m = self.m
         return [m.dropout.p] + [p for blk in m.ca.layer for p in (blk.attn.proj_drop.p, blk.ffn.dropout.p)]
 
-    def gemm(self, tA, tB, M, N, K, A, lda, Bm, ldb, C, ldc, bias=None, add=None, add_ld=0, bias_grad=None):
-        self.L.vc_gemm_ex(tA, tB, M, N, K, 1.0, A, lda, 0, Bm, ldb, 0, 0.0, C, ldc, 0, 1, bias, add, add_ld, 0, 0,
-                          bias_grad, self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
-
     # ------------------------------------------------------------ forward
     def _forward(self):
         m, L, B, Pp, P, s = self.m, self.L, self.B, self.Pp, self.P, self.s

@@ -36,13 +36,12 @@ import torch.nn as nn
 from . import program, seeds
 from ._lib import lib
 from .flat import F32, FlatParams
-from .model import N_COUNTERS
 
 LN_EPS = 1e-5
 DIM = 64
 T = 65
 HS_HEADS = 16
-EN_HEADS, EN_DIM_HEAD = 4, 16
+EN_HEADS, EN_DIM_HEAD = program.ATTN_HEADS, program.ATTN_DIM_HEAD
 PATCH = 8
 EMBED_PART = 1156   # VC_MHST_EMBED_PART
 POOL_FLOATS = 132   # VC_MHST_POOL_FLOATS
@@ -50,6 +49,8 @@ NCLS_MAX = 256      # vc_mhst_tail_*
 PY_KERNELS = (3, 5, 7, 9)
 SPECTRAL_TAPS = (1, 3, 5, 11)
 GATE_SITE = 100000  # the gates' seed sites start here, clear of the dropout sites
+# en_transformer (MHST.py:220-247) as program.encoder_fwd / _bwd take it: pre-norm layers over the 65 tokens
+ENCODER = dict(prefix="en_transformer", T=T, D=DIM, ff="mlp", site="en")
 
 
 # ---------------------------------------------------------------- parameter tree (reference names)
@@ -315,51 +316,6 @@ class _Program(program.Program):
         self.seed_dropout(self.train)
 
     # ------------------------------------------------------------ helpers
-    def p(self, mod):
-        return float(mod.p) if self.train else 0.0
-
-    def bytes(self, *shape):
-        return torch.empty(*shape, dtype=torch.uint8, device=self.dev)
-
-    def gemm(self, tA, tB, M, N, K, A, lda, Bm, ldb, C, ldc, beta=0.0, bias=None, bias_grad=None):
-        self.L.vc_gemm_ex(tA, tB, M, N, K, 1.0, A, lda, 0, Bm, ldb, 0, beta, C, ldc, 0, 1, bias, None, 0, 0, 0,
-                          bias_grad, self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
-
-    def linear(self, x, M, K, N, pfx, bias=True):
-        y = self.new(M, N)
-        self.gemm(0, 1, M, N, K, x.data_ptr(), K, self.P[pfx + ".weight"], K, y.data_ptr(), N,
-                  bias=self.P[pfx + ".bias"] if bias else None)
-        return y
-
-    def linear_bwd(self, dy, x, M, K, N, pfx, bias=True, need_dx=True):
-        """dW (+ db) of y = x W^T + b into the flat gradient; returns dx"""
-        self.gemm(1, 0, N, K, M, dy.data_ptr(), N, x.data_ptr(), K, self.G[pfx + ".weight"], K,
-                  bias_grad=self.G[pfx + ".bias"] if bias else None)
-        if not need_dx:
-            return None
-        dx = self.new(M, K)
-        self.gemm(0, 0, M, K, N, dy.data_ptr(), N, self.P[pfx + ".weight"], K, dx.data_ptr(), K)
-        return dx
-
-    def dropped(self, site, x, add, n, p):
-        """add + dropout_p(x) as a new tensor (x + add, or x itself, at p = 0)"""
-        if p > 0:
-            y = torch.empty_like(x)
-            self.drop(site, x, add, y, n, p)
-            return y
-        if add is None:
-            return x
-        y = torch.empty_like(x)
-        self.L.vc_add2_2d(n // DIM, DIM, x.data_ptr(), DIM, add.data_ptr(), DIM, y.data_ptr(), DIM, 0.0, self.s)
-        return y
-
-    def drop_bwd(self, site, dy, n, p):
-        if p <= 0:
-            return dy
-        dx = torch.empty_like(dy)
-        self.L.vc_dropout_bwd(n, dy.data_ptr(), self.masks[site].data_ptr(), p, dx.data_ptr(), self.s)
-        return dx
-
     def conv(self, shape, x, ldx, w, bias, y, ycol, ldy):
         self.L.vc_mhst_conv_fwd(self.B, *shape, x.data_ptr(), ldx, self.P[w], self.P[bias] if bias else None,
                                 y.data_ptr() + F32 * ycol, ldy, self.s)
@@ -371,24 +327,6 @@ class _Program(program.Program):
         if dx is not None:
             L.vc_mhst_conv_dgrad(self.B, *shape, dy.data_ptr() + F32 * ycol, ldy, self.P[w], dx.data_ptr(), ldx, beta,
                                  self.s)
-
-    def bn_bwd(self, pfx, dz, y, mean, inv, M, C):
-        dy = self.new(M, C)
-        self.L.vc_bn_bwd_relu_ex(1 if self.train else 0, M, C, dz.data_ptr(), C, y.data_ptr(), C, mean.data_ptr(),
-                                 inv.data_ptr(), self.P[pfx + ".weight"], self.P[pfx + ".bias"], dy.data_ptr(), C, 0.0,
-                                 self.G[pfx + ".weight"], self.G[pfx + ".bias"], 0.0, self.scr.data_ptr(), self.SCRATCH,
-                                 self.cnt, N_COUNTERS, self.s)
-        return dy
-
-    def ln_bwd(self, pfx, dY, X, ldx, mu, rs, R, dx, lddx, beta):
-        self.L.vc_layernorm_bwd(R, DIM, dY.data_ptr(), DIM, X, ldx, self.P[pfx + ".weight"], mu.data_ptr(),
-                                rs.data_ptr(), dx, lddx, beta, self.G[pfx + ".weight"], self.G[pfx + ".bias"], 0.0,
-                                self.scr.data_ptr(), self.SCRATCH, self.s)
-
-    def reduce_part(self, part, width, col, n, out):
-        """out[0:n] = sum over the samples of part[b][col : col + n] (fixed order)"""
-        self.L.vc_colsum(self.B, n, part.data_ptr() + F32 * col, width, out, 0.0, self.scr.data_ptr(), self.SCRATCH,
-                         self.s)
 
     # the conv shapes (D, H, W, C, O, G, KD, KS, sd, pd, Dout) of the model
     def shapes(self):
@@ -451,13 +389,13 @@ class _Program(program.Program):
         L.vc_mhst_embed_fwd(B, ph.data_ptr(), pl.data_ptr(), P["weight_hsi"], P["weight_lidar"],
                             P["encoder_embedding.weight"], P["encoder_embedding.bias"], P["encoder_pos_embed"],
                             P["cls_token"], xcnn.data_ptr(), Xe.data_ptr(), s)
-        self.pe = self.p(m.dropout)
-        X = self.dropped("emb", Xe, None, B * T * DIM, self.pe)
+        self.pe = self.drop_p(m.dropout)
+        X = self.dropped("emb", Xe, None, B * T * DIM, self.pe, DIM)
         sv.update(y1=y1, z1=z1, mean1=mean1, inv1=inv1, y2=y2, z2=z2, mean2=mean2, inv2=inv2, y3=y3, z3=z3, mean3=mean3,
                   inv3=inv3, y4=y4, z4=z4, mean4=mean4, inv4=inv4, y5=y5, mean5=mean5, inv5=inv5, ph=ph, argh=argh,
                   x2r=x2r, ld2=ld2, yl1=yl1, zl1=zl1, meanl1=meanl1, invl1=invl1, yl2=yl2, zl2=zl2, meanl2=meanl2,
                   invl2=invl2, yl3=yl3, meanl3=meanl3, invl3=invl3, pl=pl, argl=argl, xcnn=xcnn)
-        X = self.encoder_fwd(X)
+        X, self.enc = self.encoder_fwd(X, layers=m.en_transformer.layers, hidden=m.mlp_dim, **ENCODER)
         X = self.headselect_fwd(X)
         # classifier (:308-319): the transformer's cls row through HeadSelectViT.norm and mlp_head ...
         Yn, mun, rsn = self.ln("HeadSelectViT.norm", X.data_ptr(), B, T * DIM)
@@ -493,33 +431,6 @@ class _Program(program.Program):
         pool = {k: (a.view(B, 16, 64).cpu(), v.view(B, 16, 64).cpu()) for k, (a, v) in self.dec["pool"].items()}
         return dict(relu=relu, pool=pool)
 
-    def encoder_fwd(self, X):
-        """en_transformer (MHST.py:220-247): pre-norm layers of 4 heads of 16 over the 65 tokens, on S2EFT's kernels"""
-        m, L, B, P = self.m, self.L, self.B, self.P
-        R, E, Hd = B * T, EN_HEADS * EN_DIM_HEAD, m.mlp_dim
-        self.enc = []
-        for li in range(m.en_depth):
-            pre = f"en_transformer.layers.{li}"
-            att, ff = m.en_transformer.layers[li][0].fn.fn, m.en_transformer.layers[li][1].fn.fn
-            pa, p1, p2 = self.p(att.to_out[1]), self.p(ff.mlp[2]), self.p(ff.mlp[4])
-            Y, mu, rs = self.ln(pre + ".0.fn.norm", X.data_ptr(), R, DIM)
-            qkv = self.linear(Y, R, DIM, 3 * E, pre + ".0.fn.fn.to_qkv", bias=False)
-            O, lse = self.new(R, E), self.new(B, EN_HEADS, T)
-            L.vc_s2eft_attn_fwd(B, T, EN_HEADS, qkv.data_ptr(), EN_DIM_HEAD ** -0.5, O.data_ptr(), lse.data_ptr(), self.s)
-            A2 = self.linear(O, R, E, DIM, pre + ".0.fn.fn.to_out.0")
-            X2 = self.dropped(f"en{li}.attn", A2, X, R * DIM, pa)
-            Y2, mu2, rs2 = self.ln(pre + ".1.fn.norm", X2.data_ptr(), R, DIM)
-            H1 = self.linear(Y2, R, DIM, Hd, pre + ".1.fn.fn.mlp.0")
-            Gl = self.new(R, Hd)
-            L.vc_gelu_fwd(R * Hd, H1.data_ptr(), Gl.data_ptr(), self.s)
-            Gd = self.dropped(f"en{li}.ff1", Gl, None, R * Hd, p1)
-            F2 = self.linear(Gd, R, Hd, DIM, pre + ".1.fn.fn.mlp.3")
-            X3 = self.dropped(f"en{li}.ff2", F2, X2, R * DIM, p2)
-            self.enc.append(dict(X=X, Y=Y, mu=mu, rs=rs, qkv=qkv, O=O, lse=lse, X2=X2, Y2=Y2, mu2=mu2, rs2=rs2, H1=H1,
-                                 Gd=Gd, pa=pa, p1=p1, p2=p2))
-            X = X3
-        return X
-
     def headselect_fwd(self, X):
         """the head-select blocks (HSPT.py:354-387)"""
         m, L, B, P, s = self.m, self.L, self.B, self.P, self.s
@@ -531,7 +442,7 @@ class _Program(program.Program):
         for i in range(m.hs_depth):
             pre = f"HeadSelectViT.blocks.{i}"
             blk = m.HeadSelectViT.blocks[i]
-            pp, pj, pm = self.p(blk.attn.attn_drop), self.p(blk.attn.proj_drop), self.p(blk.mlp.drop)
+            pp, pj, pm = self.drop_p(blk.attn.attn_drop), self.drop_p(blk.attn.proj_drop), self.drop_p(blk.mlp.drop)
             # LayerNorm, one GEMM for query | key | value, then the fused chain (DynaLinear's masked output rows :110-125,
             # Pooling.py, attention with residual pooling :254-282, proj's masked input columns), one launch: the gate
             # on the cls row (:38-63) is computed by every (sample, head) block for its own head
@@ -558,7 +469,7 @@ class _Program(program.Program):
                   P[pre + ".attn.pool_q.weight"], LN_EPS, 0.5, pp, mk.data_ptr() if mk is not None else None,
                   logits.data_ptr(), noise.data_ptr(), yg.data_ptr(), sel.data_ptr(), am.data_ptr(), s)
             pr = self.linear(am, R, DIM, DIM, pre + ".attn.proj")
-            X2 = self.dropped(f"hs{i}.proj", pr, X, R * DIM, pj)
+            X2 = self.dropped(f"hs{i}.proj", pr, X, R * DIM, pj, DIM)
             # masked MLP (:293-321)
             Y2, mu2, rs2 = self.ln(pre + ".norm2", X2.data_ptr(), R, DIM)
             ym = self.new(R, DIM)
@@ -566,9 +477,9 @@ class _Program(program.Program):
             H1 = self.linear(ym, R, DIM, Hh, pre + ".mlp.fc1")
             Gl = self.new(R, Hh)
             L.vc_gelu_fwd(R * Hh, H1.data_ptr(), Gl.data_ptr(), s)
-            Gd = self.dropped(f"hs{i}.fc1", Gl, None, R * Hh, pm)
+            Gd = self.dropped(f"hs{i}.fc1", Gl, None, R * Hh, pm, Hh)
             F2 = self.linear(Gd, R, Hh, DIM, pre + ".mlp.fc2")
-            X3 = self.dropped(f"hs{i}.fc2", F2, X2, R * DIM, pm)
+            X3 = self.dropped(f"hs{i}.fc2", F2, X2, R * DIM, pm, DIM)
             self.hs.append(dict(X=X, yg=yg, sel=sel, Y=Y, mu=mu, rs=rs, qkv=qkv, mk=mk, am=am, X2=X2, Y2=Y2, mu2=mu2,
                                 rs2=rs2, ym=ym, H1=H1, Gd=Gd, pp=pp, pj=pj, pm=pm))
             X = X3
@@ -605,13 +516,13 @@ class _Program(program.Program):
         # transformer head: mlp_head, HeadSelectViT.norm on the cls rows; every other row of dX starts at zero
         dYc = self.linear_bwd(dlg1, sv["Yc"], B, DIM, n, "mlp_head.1")
         dYn = self.new(B, DIM)
-        self.ln_bwd("mlp_head.0", dYc, sv["Yn"].data_ptr(), DIM, sv["muc"], sv["rsc"], B, dYn.data_ptr(), DIM, 0.0)
+        self.ln_bwd("mlp_head.0", dYc, sv["Yn"].data_ptr(), DIM, sv["muc"], sv["rsc"], B, DIM, dYn.data_ptr(), DIM, 0.0)
         dX = self.new(B * T, DIM)
         L.vc_fill(B * T * DIM, dX.data_ptr(), 0.0, s)
-        self.ln_bwd("HeadSelectViT.norm", dYn, sv["Xlast"].data_ptr(), T * DIM, sv["mun"], sv["rsn"], B, dX.data_ptr(),
-                    T * DIM, 0.0)
+        self.ln_bwd("HeadSelectViT.norm", dYn, sv["Xlast"].data_ptr(), T * DIM, sv["mun"], sv["rsn"], B, DIM,
+                    dX.data_ptr(), T * DIM, 0.0)
         dX = self.headselect_bwd(dX)
-        dX = self.encoder_bwd(dX)
+        dX = self.encoder_bwd(dX, self.enc, hidden=m.mlp_dim, **ENCODER)
         # embedding
         dXe = self.drop_bwd("emb", dX, B * T * DIM, self.pe)
         dph, dpl = self.new(B * 16, 64), self.new(B * 16, 64)
@@ -687,7 +598,8 @@ class _Program(program.Program):
                                    dsel.data_ptr(), 0.0, s)
             dX2 = self.new(R, DIM)
             L.vc_add2_2d(R, DIM, dX.data_ptr(), DIM, None, 0, dX2.data_ptr(), DIM, 0.0, s)
-            self.ln_bwd(pre + ".norm2", dY2, st["X2"].data_ptr(), DIM, st["mu2"], st["rs2"], R, dX2.data_ptr(), DIM, 1.0)
+            self.ln_bwd(pre + ".norm2", dY2, st["X2"].data_ptr(), DIM, st["mu2"], st["rs2"], R, DIM, dX2.data_ptr(), DIM,
+                        1.0)
             # attention: X2 = X + drop(proj(mask(attn(pool(mask(qkv(LN1(X))))))))
             dpr = self.drop_bwd(f"hs{i}.proj", dX2, R * DIM, st["pj"])
             dam = self.linear_bwd(dpr, st["am"], R, DIM, DIM, pre + ".attn.proj")
@@ -708,41 +620,13 @@ class _Program(program.Program):
                       DIM)
             dXi = self.new(R, DIM)
             L.vc_add2_2d(R, DIM, dX2.data_ptr(), DIM, None, 0, dXi.data_ptr(), DIM, 0.0, s)
-            self.ln_bwd(pre + ".norm1", dY, st["X"].data_ptr(), DIM, st["mu"], st["rs"], R, dXi.data_ptr(), DIM, 1.0)
+            self.ln_bwd(pre + ".norm1", dY, st["X"].data_ptr(), DIM, st["mu"], st["rs"], R, DIM, dXi.data_ptr(), DIM,
+                        1.0)
             # the gate's Linear on the cls rows (ld T * DIM)
             gp = pre + ".head_select.mlp_head"
             self.gemm(1, 0, HS_HEADS, DIM, B, dlg.data_ptr(), HS_HEADS, st["X"].data_ptr(), T * DIM, G[gp + ".weight"], DIM,
                       bias_grad=G[gp + ".bias"])
             self.gemm(0, 0, B, DIM, HS_HEADS, dlg.data_ptr(), HS_HEADS, P[gp + ".weight"], DIM, dXi.data_ptr(), T * DIM,
                       beta=1.0)
-            dX = dXi
-        return dX
-
-    def encoder_bwd(self, dX):
-        m, L, B, P = self.m, self.L, self.B, self.P
-        R, E, Hd = B * T, EN_HEADS * EN_DIM_HEAD, m.mlp_dim
-        G = self.G
-        for li in reversed(range(m.en_depth)):
-            pre = f"en_transformer.layers.{li}"
-            st = self.enc[li]
-            dF2 = self.drop_bwd(f"en{li}.ff2", dX, R * DIM, st["p2"])
-            dGd = self.linear_bwd(dF2, st["Gd"], R, Hd, DIM, pre + ".1.fn.fn.mlp.3")
-            dGl = self.drop_bwd(f"en{li}.ff1", dGd, R * Hd, st["p1"])
-            dH1 = self.new(R, Hd)
-            L.vc_gelu_bwd(R * Hd, dGl.data_ptr(), st["H1"].data_ptr(), dH1.data_ptr(), self.s)
-            dY2 = self.linear_bwd(dH1, st["Y2"], R, DIM, Hd, pre + ".1.fn.fn.mlp.0")
-            dX2 = self.new(R, DIM)
-            L.vc_add2_2d(R, DIM, dX.data_ptr(), DIM, None, 0, dX2.data_ptr(), DIM, 0.0, self.s)
-            self.ln_bwd(pre + ".1.fn.norm", dY2, st["X2"].data_ptr(), DIM, st["mu2"], st["rs2"], R, dX2.data_ptr(), DIM,
-                        1.0)
-            dA2 = self.drop_bwd(f"en{li}.attn", dX2, R * DIM, st["pa"])
-            dO = self.linear_bwd(dA2, st["O"], R, E, DIM, pre + ".0.fn.fn.to_out.0")
-            dqkv = self.new(R, 3 * E)
-            L.vc_s2eft_attn_bwd(B, T, EN_HEADS, st["qkv"].data_ptr(), st["O"].data_ptr(), dO.data_ptr(),
-                                st["lse"].data_ptr(), EN_DIM_HEAD ** -0.5, dqkv.data_ptr(), self.s)
-            dY = self.linear_bwd(dqkv, st["Y"], R, DIM, 3 * E, pre + ".0.fn.fn.to_qkv", bias=False)
-            dXi = self.new(R, DIM)
-            L.vc_add2_2d(R, DIM, dX2.data_ptr(), DIM, None, 0, dXi.data_ptr(), DIM, 0.0, self.s)
-            self.ln_bwd(pre + ".0.fn.norm", dY, st["X"].data_ptr(), DIM, st["mu"], st["rs"], R, dXi.data_ptr(), DIM, 1.0)
             dX = dXi
         return dX
