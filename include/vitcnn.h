@@ -953,7 +953,35 @@ VC_API int vc_pca_project(long n, int C, long ld, int K, const float* x, const f
  *   part[(b 16 + h)] = the head's share of the 132 pooling parameter gradients (VC_MHST_POOL_FLOATS per row, B 16 rows;
  *   the caller sums them in row order), and
  *     dlogits[b,h] = (dsel_in[b,h] + sum dAM ao + sum dqm QKV) y (1 - y) gscale     (dsel_in: the MLP mask's share, may
- *   be null; gscale = 1 / tau in training, 1 in eval; the sums in a fixed order). */
+ *   be null; gscale = 1 / tau in training, 1 in eval; the sums in a fixed order).
+ *
+ * vc_mhst_pconv_ok / _ws_floats / _fwd / _dgrad / _wgrad (csrc/mhst_pconv.hip): the grouped "whole-depth" convolutions
+ *   of the pyramidal stages on 8 x 8 maps as implicit GEMMs on v_mfma_f32_16x16x4_f32, exact fp32 (an MFMA is a k-ordered
+ *   fmaf chain).  Exactly vc_mhst_conv_fwd / _dgrad / _wgrad at H = W = 8, KD = D, sd = 1, pd = 0, Dout = 1:
+ *     y[b,h,w,o] = bias[o] + sum_{d,kh,kw,c < C/G} w[o][c][d][kh][kw] x[b, d, h - KS/2 + kh, w - KS/2 + kw,
+ *                  (o / (O/G)) (C/G) + c]
+ *   with the same operands: x rows (b, d, h, w) of C channels (ldx), w [O][C/G][D][KS][KS] dense, y rows (b, h, w) of O
+ *   columns written at the caller's column offset inside rows of ldy; dgrad: dx = beta dx + the transposed sum; wgrad:
+ *   dw (overwritten) and db (may be null) = the column sums of dy.
+ *   vc_mhst_pconv_ok(D, C, O, G, KS, ldx, ldy) is 1 where the family takes the shape (host arithmetic only): KS odd in
+ *   3..9, C a multiple of 16, G dividing C and O, C / G a power of two in 2..32, O / G a power of two in 2..16,
+ *   1 <= D <= 4096, ldx >= C, ldy >= O (the model's hsi_encoder.conv4, lidar_encoder.conv2 and pyconv_classifier.conv1;
+ *   lidar_encoder.conv1 with its 1 to 3 input channels stays on vc_mhst_conv_*).  Alignment contract: ldx and ldy are multiples of 4 floats and the x-side pointer (x, dx), the y-side
+ *   pointer as passed (y, dy: base + column offset, so an offset that is a multiple of 4 floats; the model's are
+ *   multiples of 16) and ws are 16-byte aligned; w, bias, dw, db need only their natural alignment.
+ *   Per group each direction is a skinny GEMM whose N is padded to 16 with zero weights:
+ *     fwd    M = (b, position), N = O/G, K = (tap, depth, channel); a block per (2 samples, group, chunk of
+ *            VC_MHST_PCONV_CHUNK depths; half that at C/G = 32), the chunk's planes in LDS; more than one chunk: partials
+ *            [chunk][b 64][O] in ws, summed in chunk order
+ *     dgrad  M = (b, position), N = (depth, channel) in tiles of 16, K = (tap, output)
+ *     wgrad  M = O/G, N = (depth, channel) in tiles of 16, K = (b, position) per tap; a block per (group, tile, kernel
+ *            row, sample split), its 4 waves summed in wave order, the splits' partials in ws summed in split order
+ *   fwd and dgrad first re-lay the weight [k][16] into ws (a pack launch per call; dgrad instead keeps a
+ *   group's weight of up to 8192 floats in LDS as it lies).  ws: vc_mhst_pconv_ws_floats(B, ...)
+ *   floats, the max over the three directions (-1 on a shape _ok refuses).  Only a group's own columns are read; a tap
+ *   outside the map feeds 0 without a read, so row padding and neighbouring columns may hold anything.  Invalid
+ *   arguments, a shape _ok refuses and a workspace that is too small return 1 before any launch. */
+#define VC_MHST_PCONV_CHUNK 4
 #define VC_MHST_CONV3_WAVES 512
 #define VC_MHST_EMBED_PART 1156
 #define VC_MHST_POOL_FLOATS 132
@@ -973,6 +1001,14 @@ VC_API int vc_mhst_conv3_dgrad(int B, int D, const float* dy, long lddy, const f
 VC_API int vc_mhst_conv3_wgrad_ws_floats(int B, int D);
 VC_API int vc_mhst_conv3_wgrad(int B, int D, const float* x, long ldx, const float* dy, long lddy, float* dw, float* ws,
                                long ws_floats, hipStream_t stream);
+VC_API int vc_mhst_pconv_ok(int D, int C, int O, int G, int KS, long ldx, long ldy);
+VC_API int vc_mhst_pconv_ws_floats(int B, int D, int C, int O, int G, int KS);
+VC_API int vc_mhst_pconv_fwd(int B, int D, int C, int O, int G, int KS, const float* x, long ldx, const float* w,
+                             const float* bias, float* y, long ldy, float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_mhst_pconv_dgrad(int B, int D, int C, int O, int G, int KS, const float* dy, long lddy, const float* w,
+                               float* dx, long lddx, float beta, float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_mhst_pconv_wgrad(int B, int D, int C, int O, int G, int KS, const float* x, long ldx, const float* dy,
+                               long lddy, float* dw, float* db, float* ws, long ws_floats, hipStream_t stream);
 VC_API int vc_mhst_embed_fwd(int B, const float* ph, const float* pl, const float* wh, const float* wl, const float* W,
                              const float* bias, const float* pos, const float* cls, float* xcnn, float* X0,
                              hipStream_t stream);

@@ -2,10 +2,13 @@
 registry's model at B = 64, dropout 0.1, 16 classes, at 144 + 1 and at 30 + 1 bands: `TrainStepper.step` eager
 (`use_graph=False`) and captured (`capture_step=True`: one hipGraph replay per step, fresh masks and gate noise from the
 device-side seed), the kernel launches per step and the five largest kernels of the eager step with their share of the
-device time (torch.profiler, a separate pass); then the 3x3x3 convolution's three MFMA kernels, the direct form of its
-forward and the pyramidal convolution forward alone (HIP events) with their fraction of the fp32 MFMA peak (157.3
-TFLOP/s).  DESIGN.md section 28 records the output.
-usage: python tools/mhst_step.py [K] [--no-profile]"""
+device time (torch.profiler, a separate pass); then the 3x3x3 convolution's three MFMA kernels and the direct form of its
+forward alone (HIP events), and every pyramidal site kind the MFMA family accepts (`vc_mhst_pconv_ok`) in each of the
+three directions on both families, `vc_mhst_conv_*` and `vc_mhst_pconv_*`, with nominal and issued MFLOP per patch and
+the fraction of the fp32 MFMA peak (157.3 TFLOP/s).  `--conv direct|mfma|both` chooses the model's conv mode for the step
+timings; `both` times the two modes in one process, their samples interleaved (A, B, A, B, ...), as the two families'
+always are.  DESIGN.md section 28 records the output.
+usage: python tools/mhst_step.py [K] [--no-profile] [--conv direct|mfma|both]"""
 import os
 import statistics
 import sys
@@ -39,29 +42,49 @@ def timed(fn, k, dev):
     return statistics.median(ts), min(ts), max(ts)
 
 
-def build(dev, l1):
+def timed_ab(fns, k):
+    """timed() for several callables with their samples interleaved (A, B, A, B, ...): [(median, min, max)] in ms"""
+    ts = [[] for _ in fns]
+    for _ in range(k):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts[i].append(e0.elapsed_time(e1))
+    return [(statistics.median(t), min(t), max(t)) for t in ts]
+
+
+def build(dev, l1, conv="direct"):
     from vitcnn_amd import model_utils as mu
     torch.manual_seed(0)
     m, opt, crit, _ = mu.get_model("MHST", n_classes=NCLS, n_bands=(l1, 1), ignored_labels=[0], dataset="synthetic",
-                                   device=dev)
+                                   device=dev, conv=conv)
     return m.train(), opt, crit
 
 
-def run(l1, k, profile):
+def run(l1, k, profile, convs):
     from vitcnn_amd import seeds
     from vitcnn_amd.step import TrainStepper
     dev = torch.device("cuda", 0)
     x1, x2, t = batch(dev, l1)
     for use_graph in (False, True):
-        m, opt, crit = build(dev, l1)
-        seeds.attach(m, 12345)
-        st = TrainStepper(m, opt, crit, capture_step=True, use_graph=use_graph)
-        for _ in range(4):
-            st.step(x1, x2, t)
-        med, lo, hi = timed(lambda: st.step(x1, x2, t), k, dev)
-        print(f"mhst {l1}+1 bands B={B} {st.launch}: median {med:.3f} ms/step (min {lo:.3f}, max {hi:.3f}) over {k} steps",
-              flush=True)
-        if profile and not use_graph:
+        sts = []
+        for conv in convs:
+            m, opt, crit = build(dev, l1, conv)
+            seeds.attach(m, 12345)
+            st = TrainStepper(m, opt, crit, capture_step=True, use_graph=use_graph)
+            for _ in range(4):
+                st.step(x1, x2, t)
+            sts.append(st)
+        res = timed_ab([lambda st=st: st.step(x1, x2, t) for st in sts], k)
+        for conv, st, (med, lo, hi) in zip(convs, sts, res):
+            print(f"mhst {l1}+1 bands B={B} conv={conv} {st.launch}: median {med:.3f} ms/step (min {lo:.3f}, max {hi:.3f}) "
+                  f"over {k} steps", flush=True)
+        for conv, st in zip(convs, sts):
+            if not profile or use_graph:
+                continue
             from torch.profiler import ProfilerActivity, profile as prof
             try:
                 with prof(activities=[ProfilerActivity.CUDA]) as p:
@@ -72,16 +95,16 @@ def run(l1, k, profile):
                 total = sum(e.device_time_total for e in evs)
                 evs.sort(key=lambda e: -e.device_time_total)
                 for e in evs[:5]:
-                    print(f"  kernel {e.key[:90]}: {e.device_time_total / 3e3:.3f} ms/step, "
+                    print(f"  conv={conv} kernel {e.key[:90]}: {e.device_time_total / 3e3:.3f} ms/step, "
                           f"{100.0 * e.device_time_total / total:.1f}% of the device time ({e.count // 3} launches)")
-                print(f"  device time {total / 3e3:.3f} ms/step, {sum(e.count for e in evs) / 3:.0f} launches/step",
-                      flush=True)
+                print(f"  conv={conv} device time {total / 3e3:.3f} ms/step, {sum(e.count for e in evs) / 3:.0f} "
+                      f"launches/step", flush=True)
             except Exception as e:   # the profiler is optional: say so, never guess
                 print(f"  kernel shares not measured: {type(e).__name__}: {str(e)[:120]}", flush=True)
 
 
 def conv_alone(l1, k):
-    """the 3x3x3 conv and the HSI pyramidal conv (four launches) forward, alone: time and fraction of the MFMA peak"""
+    """the 3x3x3 conv alone, each direction and the direct form of its forward: time and fraction of the MFMA peak"""
     from vitcnn_amd._lib import lib
     L = lib()
     dev = torch.device("cuda", 0)
@@ -106,19 +129,9 @@ def conv_alone(l1, k):
         L.vc_mhst_conv_fwd(B, D1, 8, 8, 16, 16, 1, 3, 3, 1, 1, D1, x.data_ptr(), 16, w3.data_ptr(), b3.data_ptr(),
                            y3.data_ptr(), 16, s)
 
-    ws = [torch.rand(16 * (16 // g) * D1 * kk * kk, device=dev) for kk, g in zip((3, 5, 7, 9), (1, 2, 4, 8))]
-    y4 = torch.empty(B * 64, 64, device=dev)
-
-    def py():
-        for i, (kk, g) in enumerate(zip((3, 5, 7, 9), (1, 2, 4, 8))):
-            L.vc_mhst_conv_fwd(B, D1, 8, 8, 16, 16, g, D1, kk, 1, 0, 1, x.data_ptr(), 16, ws[i].data_ptr(), None,
-                               y4.data_ptr() + 64 * i, 64, s)
-
     f3 = 2.0 * B * D1 * 64 * 16 * 432
-    fp = 2.0 * B * 64 * 16 * sum((16 // g) * D1 * kk * kk for kk, g in zip((3, 5, 7, 9), (1, 2, 4, 8)))
     for name, fn, fl in (("3x3x3 conv fwd (MFMA)", c3, f3), ("3x3x3 conv dgrad (MFMA)", c3d, f3),
-                         ("3x3x3 conv wgrad (MFMA, 2 launches)", c3w, f3), ("3x3x3 conv fwd (direct form)", c3direct, f3),
-                         ("pyramidal conv fwd (4 launches)", py, fp)):
+                         ("3x3x3 conv wgrad (MFMA, 2 launches)", c3w, f3), ("3x3x3 conv fwd (direct form)", c3direct, f3)):
         for _ in range(5):
             fn()
         med, lo, hi = timed(fn, k, dev)
@@ -126,12 +139,93 @@ def conv_alone(l1, k):
               f"{100.0 * fl / (lo * 1e-3) / PEAK_FP32_MFMA:.2f}% of the fp32 MFMA peak at the minimum", flush=True)
 
 
+MFMA_FLOP = 2 * 16 * 16 * 4      # one v_mfma_f32_16x16x4_f32
+CHUNK = 4                        # VC_MHST_PCONV_CHUNK
+
+
+def issued_mflop(D, C, O, G, KS):
+    """MFMA work per patch that csrc/mhst_pconv.hip issues (N padded to 16, tiles and taps wholly outside the map
+    skipped), per direction, by the kernels' own loop structure"""
+    cg, og, ps, KK = C // G, O // G, KS // 2, KS * KS
+    inside = lambda v: 0 <= v < 8   # noqa: E731
+    chunk = CHUNK if cg <= 16 else CHUNK // 2
+    ksteps = sum((min(chunk, D - d0) * cg + 3) // 4 for d0 in range(0, D, chunk))
+    rows = sum(1 for t in range(4) for kh in range(KS) if inside(2 * t + kh - ps) or inside(2 * t + 1 + kh - ps))
+    fwd = G * ksteps * rows * KS
+    NT, Kd = (D * cg + 15) // 16, (og * KK + 3) // 4 * 4
+    steps = 0
+    for tile in range(4):
+        for i in range(Kd // 4):
+            taps = {(4 * i + kq) // og for kq in range(4) if 4 * i + kq < og * KK}
+            if any(inside(p // 8 + ps - tp // KS) and inside(p % 8 + ps - tp % KS)
+                   for tp in taps for p in range(tile * 16, tile * 16 + 16)):
+                steps += 1
+    dgrad = G * NT * steps
+    wsteps = sum(1 for kh in range(KS) for i in range(16) if inside(i // 2 + kh - ps)
+                 for kw in range(KS) if any(inside((i & 1) * 4 + kq + kw - ps) for kq in range(4)))
+    wgrad = G * NT * wsteps
+    return {d: n * MFMA_FLOP / 1e6 for d, n in (("fwd", fwd), ("dgrad", dgrad), ("wgrad", wgrad))}
+
+
+def pconv_sites(l1, k, fixed_sites):
+    """every site kind vc_mhst_pconv_ok accepts, each direction, direct and mfma interleaved: ms, MFLOP per patch nominal
+    and issued, fraction of the fp32 MFMA peak (nominal work over the minimum time)"""
+    from vitcnn_amd._lib import lib
+    L = lib()
+    dev = torch.device("cuda", 0)
+    s = torch.cuda.current_stream(dev).cuda_stream
+    D1 = (l1 + 2) // 3
+    sites = [(f"hsi conv4 k{kk} g{g}", D1, 16, 16, g, kk, 16, 64) for kk, g in zip((3, 5, 7, 9), (1, 2, 4, 8))]
+    if fixed_sites:   # these do not depend on the band count
+        sites += [(f"lidar conv2 k{kk}", 1, 32, 16, 1, kk, 32, 64) for kk in (3, 5, 7, 9)]
+        sites += [(f"classifier conv1 k{kk} g2", 1, 64, 16, 2, kk, 64, 32) for kk in (3, 5)]
+    for name, D, C, O, G, KS, ldx, ldy in sites:
+        assert L.vc_mhst_pconv_ok(D, C, O, G, KS, ldx, ldy) == 1
+        x, dx = torch.rand(B * D * 64, ldx, device=dev), torch.zeros(B * D * 64, ldx, device=dev)
+        w, dw = torch.rand(O * (C // G) * D * KS * KS, device=dev) - 0.5, torch.empty(O * (C // G) * D * KS * KS, device=dev)
+        y, dy = torch.empty(B * 64, ldy, device=dev), torch.rand(B * 64, ldy, device=dev)
+        n = L.vc_mhst_pconv_ws_floats(B, D, C, O, G, KS)
+        ws = torch.empty(n, device=dev)
+        d = (D, 8, 8, C, O, G, D, KS, 1, 0, 1)
+        a = (D, C, O, G, KS)
+        P = lambda t: t.data_ptr()   # noqa: E731
+        pairs = {
+            "fwd": (lambda: L.vc_mhst_conv_fwd(B, *d, P(x), ldx, P(w), None, P(y), ldy, s),
+                    lambda: L.vc_mhst_pconv_fwd(B, *a, P(x), ldx, P(w), None, P(y), ldy, P(ws), n, s)),
+            "dgrad": (lambda: L.vc_mhst_conv_dgrad(B, *d, P(dy), ldy, P(w), P(dx), ldx, 0.0, s),
+                      lambda: L.vc_mhst_pconv_dgrad(B, *a, P(dy), ldy, P(w), P(dx), ldx, 0.0, P(ws), n, s)),
+            "wgrad": (lambda: L.vc_mhst_conv_wgrad(B, *d, P(x), ldx, P(dy), ldy, P(dw), None, s),
+                      lambda: L.vc_mhst_pconv_wgrad(B, *a, P(x), ldx, P(dy), ldy, P(dw), None, P(ws), n, s)),
+        }
+        nominal = 2.0 * 64 * O * (C // G) * D * KS * KS / 1e6
+        issued = issued_mflop(D, C, O, G, KS)
+        for direction, fns in pairs.items():
+            for fn in fns:
+                for _ in range(3):
+                    fn()
+            (dm, dlo, dhi), (mm, mlo, mhi) = timed_ab(fns, k)
+            verdict = "mfma wholly below direct" if mhi < dlo else "RANGES OVERLAP" if mlo <= dhi else "direct below mfma"
+            print(f"  {l1} bands {name} D={D} {direction}: direct median {dm:.4f} ms (min {dlo:.4f}, max {dhi:.4f}), mfma "
+                  f"median {mm:.4f} ms (min {mlo:.4f}, max {mhi:.4f}), {nominal:.2f} MFLOP/patch nominal, "
+                  f"{issued[direction]:.2f} issued, mfma at {100.0 * nominal * 1e6 * B / (mlo * 1e-3) / PEAK_FP32_MFMA:.2f}% "
+                  f"of the fp32 MFMA peak (direct {100.0 * nominal * 1e6 * B / (dlo * 1e-3) / PEAK_FP32_MFMA:.2f}%): "
+                  f"{verdict}", flush=True)
+
+
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    args = [a for a in sys.argv[1:] if not a.startswith("--") or a == "--conv"]
+    conv = "direct"
+    if "--conv" in args:
+        i = args.index("--conv")
+        conv = args[i + 1]
+        del args[i:i + 2]
+    if conv not in ("direct", "mfma", "both"):
+        raise SystemExit("--conv takes direct, mfma or both")
     k = int(args[0]) if args else 30
     for l1 in (144, 30):
-        run(l1, k, "--no-profile" not in sys.argv)
+        run(l1, k, "--no-profile" not in sys.argv, ("direct", "mfma") if conv == "both" else (conv,))
         conv_alone(l1, k)
+        pconv_sites(l1, k, fixed_sites=l1 == 144)
 
 
 if __name__ == "__main__":

@@ -77,7 +77,10 @@ class _Lib:
             fn.argtypes = types
             fn.restype = ctypes.c_int
             self.raw[name] = fn
-            setattr(self, name, self._size(name, fn) if name.endswith("_floats") else self._checked(name, fn))
+            if name.endswith("_ok"):   # a predicate (host arithmetic only): its 0 / 1 is the answer, not a status
+                setattr(self, name, fn)
+            else:
+                setattr(self, name, self._size(name, fn) if name.endswith("_floats") else self._checked(name, fn))
 
     @staticmethod
     def _size(name, fn):

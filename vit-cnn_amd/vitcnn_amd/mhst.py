@@ -25,6 +25,12 @@ gates' logistic noise come from the package's counter hash, seeded by `program.s
 under `seeds.attach`).  `forward(hsi, lidar, gate_noise=[depth, B, 16])` takes the noise (g1 - g2 of the reference's two
 Gumbel draws) from the caller instead; the program keeps what it used in `noise`, the decisions in `sel`.
 
+`conv` (keyword only, `set_conv`; the positional signature and the state_dict are the reference's): "direct", the
+default and the recorded program, or "mfma": every pyramidal site whose shape `vc_mhst_pconv_ok` accepts
+(`hsi_encoder.conv4`, `lidar_encoder.conv2`, `pyconv_classifier.conv1`) runs forward, data and weight gradient through
+`vc_mhst_pconv_*`, exact-fp32 implicit GEMMs on the MFMA, in train, eval and `test()`; the strided
+`hsi_encoder.conv1`, the spectral convs and `lidar_encoder.conv1` stay on `vc_mhst_conv_*`.
+
 The patch side is 8 (`encoder_embedding` is Linear(16, 64) and `PoolAttention.hw_shape` (8, 8)); any HSI and LiDAR
 band count >= 1.
 """
@@ -207,8 +213,9 @@ class MHST(FlatParams, nn.Module):
     def __init__(self, l1, l2, patch_size, num_patches, num_classes, encoder_embed_dim, en_depth, en_heads, mlp_dim,
                  dim_head=16, dropout=0., emb_dropout=0., coefficient_hsi=0.5, coefficient_vit=0.5, hsp_vit_depth=12,
                  hsp_vit_num_heads=16, vit_qkv_bias=True, use_head_select=True, head_tau=5, mlp_ratio=4.,
-                 attnproj_mlp_drop=0., attn_drop=0.):
+                 attnproj_mlp_drop=0., attn_drop=0., *, conv="direct"):
         super().__init__()
+        self.conv = _check_conv(conv)
         _check_supported(l1, l2, patch_size, num_classes, encoder_embed_dim, en_depth, en_heads, mlp_dim, dim_head,
                          dropout, emb_dropout, hsp_vit_depth, hsp_vit_num_heads, vit_qkv_bias, use_head_select, head_tau,
                          mlp_ratio, attnproj_mlp_drop, attn_drop)
@@ -237,6 +244,13 @@ class MHST(FlatParams, nn.Module):
         self._build_flat()
         _check_packed(self)
 
+    def set_conv(self, conv: str):
+        """The family behind the pyramidal convolutions: "direct" (`vc_mhst_conv_*`) or "mfma" (`vc_mhst_pconv_*` at every
+        site whose shape `vc_mhst_pconv_ok` accepts).  Every forward builds its program from the current value; a
+        TrainStepper's captured graphs are bound to the mode they recorded and are dropped when it changes."""
+        self.conv = _check_conv(conv)
+        return self
+
     def forward(self, hsi: torch.Tensor, lidar: torch.Tensor, gate_noise: torch.Tensor = None) -> torch.Tensor:
         if hsi.device.type != "cuda" or lidar.device.type != "cuda":
             raise RuntimeError("MHST MI355X path: inputs must be on a ROCm (cuda) device; no CPU fallback")
@@ -257,6 +271,15 @@ class MHST(FlatParams, nn.Module):
         if gate_noise is None:
             return program.run(self, _Program, hsi, lidar)
         return program.run(self, _Program, hsi, lidar, gate_noise)
+
+
+CONV_MODES = ("direct", "mfma")
+
+
+def _check_conv(conv):
+    if conv not in CONV_MODES:
+        raise ValueError(f"MHST: conv must be one of {CONV_MODES}, got {conv!r}")
+    return conv
 
 
 def _check_supported(l1, l2, patch_size, num_classes, dim, en_depth, en_heads, mlp_dim, dim_head, dropout, emb_dropout,
@@ -311,17 +334,51 @@ class _Program(program.Program):
         # ONE workspace for the GEMMs' split-K slabs, vc_colsum / BatchNorm partials and the 3x3x3 weight gradient's
         # per-wave partials: every launch of the program is on one stream, in order, and each kernel has consumed its
         # partials when it ends, so no two users overlap.  A second stream would need a workspace of its own.
-        self.scratch(max(1 << 22, part, self.L.vc_mhst_conv3_wgrad_ws_floats(self.B, self.D1)), grow=True)
+        self.mfma = m.conv == "mfma"
+        pws = max(self.pconv_ws(shp) for kind in self.shapes().values()
+                  for shp in (kind if isinstance(kind, list) else [kind])) if self.mfma else 0
+        self.scratch(max(1 << 22, part, self.L.vc_mhst_conv3_wgrad_ws_floats(self.B, self.D1), pws), grow=True)
         self.noise_in = gate_noise
         self.seed_dropout(self.train)
 
     # ------------------------------------------------------------ helpers
+    @staticmethod
+    def pconv_args(shape):
+        """(D, C, O, G, KS) of a conv shape that is a whole-depth convolution on the 8 x 8 map, else None"""
+        D, H, W, C, O, G, KD, KS, sd, pd, Dout = shape
+        return (D, C, O, G, KS) if (H, W, KD, sd, pd, Dout) == (8, 8, D, 1, 0, 1) else None
+
+    def pconv(self, shape, ldx, ldy):
+        """vc_mhst_pconv_*'s shape arguments where the model runs in "mfma" mode and the family takes the site"""
+        a = self.pconv_args(shape) if self.mfma else None
+        return a if a is not None and self.L.vc_mhst_pconv_ok(*a, ldx, ldy) else None
+
+    def pconv_ws(self, shape):
+        a = self.pconv_args(shape)
+        if a is None or not self.L.vc_mhst_pconv_ok(*a, a[1] + (-a[1] % 4), a[2] + (-a[2] % 4)):
+            return 0
+        return self.L.vc_mhst_pconv_ws_floats(self.B, *a)
+
     def conv(self, shape, x, ldx, w, bias, y, ycol, ldy):
+        a = self.pconv(shape, ldx, ldy)
+        if a is not None:
+            self.L.vc_mhst_pconv_fwd(self.B, *a, x.data_ptr(), ldx, self.P[w], self.P[bias] if bias else None,
+                                     y.data_ptr() + F32 * ycol, ldy, self.scr.data_ptr(), self.SCRATCH, self.s)
+            return
         self.L.vc_mhst_conv_fwd(self.B, *shape, x.data_ptr(), ldx, self.P[w], self.P[bias] if bias else None,
                                 y.data_ptr() + F32 * ycol, ldy, self.s)
 
     def conv_bwd(self, shape, x, ldx, w, bias, dy, ycol, ldy, dx=None, beta=0.0):
         L = self.L
+        a = self.pconv(shape, ldx, ldy)
+        if a is not None:
+            scr, ns = self.scr.data_ptr(), self.SCRATCH
+            L.vc_mhst_pconv_wgrad(self.B, *a, x.data_ptr(), ldx, dy.data_ptr() + F32 * ycol, ldy, self.G[w],
+                                  self.G[bias] if bias else None, scr, ns, self.s)
+            if dx is not None:
+                L.vc_mhst_pconv_dgrad(self.B, *a, dy.data_ptr() + F32 * ycol, ldy, self.P[w], dx.data_ptr(), ldx, beta,
+                                      scr, ns, self.s)
+            return
         L.vc_mhst_conv_wgrad(self.B, *shape, x.data_ptr(), ldx, dy.data_ptr() + F32 * ycol, ldy, self.G[w],
                              self.G[bias] if bias else None, self.s)
         if dx is not None:

@@ -282,9 +282,11 @@ def _get_mhst(n_bands, n_bands2, n_classes, device, kwargs):
     """MHST branch of model_utils.py:314-335: MHST(l1, l2, patch 8, width 64, en_depth 5 of 4 heads, mlp_dim 8, dropout
     0.1, coefficient_hsi 0.6, coefficient_vit 0.7, 8 head-select blocks of 16 heads, tau 5, no qkv bias, mlp_ratio 4),
     AdamW(lr 8e-4), weighted CE over the model's mixture of probabilities, epoch 1000, batch 64; under applyPCA the
-    model is built for 30 bands."""
+    model is built for 30 bands.  `conv="mfma"`: the pyramidal convolutions on the fp32 MFMA (`MHST.set_conv`, DESIGN.md
+    section 28); the default "direct" is the recorded program."""
     from .mhst import MHST
     kwargs.setdefault("patch_size", 8)
+    conv = kwargs.setdefault("conv", "direct")
     kwargs.setdefault("applyPCA", False)
     if kwargs["applyPCA"]:
         n_bands = 30
@@ -292,7 +294,8 @@ def _get_mhst(n_bands, n_bands2, n_classes, device, kwargs):
     model = MHST(l1=n_bands, l2=n_bands2, patch_size=kwargs["patch_size"], num_patches=64, num_classes=n_classes,
                  encoder_embed_dim=64, en_depth=5, en_heads=4, mlp_dim=8, dropout=0.1, emb_dropout=0.1,
                  coefficient_hsi=0.6, coefficient_vit=0.7, hsp_vit_depth=8, hsp_vit_num_heads=16, head_tau=5,
-                 use_head_select=True, vit_qkv_bias=False, mlp_ratio=4, attnproj_mlp_drop=0.1, attn_drop=0.1).to(device)
+                 use_head_select=True, vit_qkv_bias=False, mlp_ratio=4, attnproj_mlp_drop=0.1, attn_drop=0.1,
+                 conv=conv).to(device)
     lr = kwargs.setdefault("lr", 8e-4)
     optimizer = AdamW(model.parameters(), lr=lr)
     criterion = CrossEntropyLoss(weight=kwargs["weights"])

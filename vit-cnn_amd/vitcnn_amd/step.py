@@ -166,10 +166,10 @@ class TrainStepper:
             # FlatParams re-packs into a NEW flat buffer on every device move / parameter replacement (buffers move
             # with it: nn.Module._apply), so its address stands for the module's storage; plus the optimizer state
             # and the seed state the launches were recorded with, and the model's precision where it has one (FusAtNet:
-            # the recorded conv launches carry it)
+            # the recorded conv launches carry it) and its conv mode (MHST: which family the graph launches)
             st = seeds.state(m)
             key = (m._flat_store.data_ptr(), id(self.opt._dev["m"]) if self.opt._dev is not None else None,
-                   st.state_ptr if st is not None else None, getattr(m, "precision", None))
+                   st.state_ptr if st is not None else None, getattr(m, "precision", None), getattr(m, "conv", None))
             if key != self.binding:
                 self.graphs, self.seen = {}, set()
                 self.binding = key
