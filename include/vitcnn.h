@@ -980,7 +980,45 @@ VC_API int vc_pca_project(long n, int C, long ld, int K, const float* x, const f
  *   group's weight of up to 8192 floats in LDS as it lies).  ws: vc_mhst_pconv_ws_floats(B, ...)
  *   floats, the max over the three directions (-1 on a shape _ok refuses).  Only a group's own columns are read; a tap
  *   outside the map feeds 0 without a read, so row padding and neighbouring columns may hold anything.  Invalid
- *   arguments, a shape _ok refuses and a workspace that is too small return 1 before any launch. */
+ *   arguments, a shape _ok refuses and a workspace that is too small return 1 before any launch.
+ *
+ * vc_mhst_conv1_ws_floats / _fwd / _wgrad and vc_mhst_sconv_ws_floats / _fwd / _dgrad / _wgrad (csrc/mhst_sconv.hip): the
+ *   front of the HSI encoder as implicit GEMMs on v_mfma_f32_16x16x4_f32, exact fp32, no atomics, every partial summed
+ *   in a fixed order.
+ *   conv1: the strided first convolution, exactly vc_mhst_conv_fwd / _wgrad at H = W = 8, C = 1, O = 16, G = 1, KD = 11,
+ *   KS = 3, sd = 3, pd = 5, Dout = D1 = (l1 + 2) / 3, any l1 >= 1:
+ *     y[b,e,h,w,o] = bias[o] + sum_{kd<11,kh<3,kw<3} w[o][kd][kh][kw] x[b, 3e - 5 + kd, h - 1 + kh, w - 1 + kw]
+ *   x the dense patch [B, l1, 8, 8], w [16][1][11][3][3] dense, y rows (b, e, h, w) of 16 columns in rows of ldy.  fwd:
+ *   M = (b, e, position), N = 16, K = (kh, kw, kd padded to 12) in 27 MFMA steps; a block per (sample,
+ *   VC_MHST_CONV1_CHUNK output depths) with their 3 (chunk - 1) + 11 input planes zero-padded in LDS, so no tap reads
+ *   global memory outside the cube.  wgrad: M = 16 outputs, N = 99 taps in 7 tiles, K = (b, e, position);
+ *   min(VC_MHST_CONV1_WAVES, B D1) waves each walk their (sample, depth) planes in order, a plane's 11 input planes
+ *   staged in LDS once, and leave a partial [dw 16 x 99 | db 16] in ws (the bias gradient is the tile's column of
+ *   ones), then summed in wave order.  db = the column sums of dy, may be null.  There is no data gradient: the input
+ *   is the patch.
+ *   sconv: the four spectral convolutions (16 -> 4 channels each, (k,1,1) kernels, k = 1, 3, 5, 11, padding k / 2, each
+ *   writing its 4 columns of the 16) as ONE convolution; with r_i = 0, 1, 2, 5:
+ *     y[(b,e,p), 4i + j] = bias_i[j] + sum_{t=-r_i..r_i} sum_{c<16} w_i[j][c][t + r_i] x[(b, e + t, p), c]
+ *   (depths outside [0, D) contribute nothing); x rows (b, d, p) of 16 channels (ldx), w_i [4][16][k_i] dense, y rows of
+ *   16 columns (ldy).  fwd: M = (b, e, position), N = 16, K = 11 depth offsets x 16 channels over the weight laid
+ *   [t][c][16] in LDS with structural zeros where |t| > r_i (issued 11 x 16 x 16 multiply-adds per row against the
+ *   nominal 20 x 16 x 4); a block per (sample, VC_MHST_SCONV_CHUNK depths), their chunk + 10 source planes in LDS.
+ *   dgrad: dx = beta dx + the sum of the four transposed convolutions, the same kernel with the operand roles swapped
+ *   and the offsets mirrored.  wgrad: M = 16 columns, N = 16 channels, one accumulator per depth offset, K = the rows;
+ *   min(VC_MHST_SCONV_BLOCKS, B ceil(D / chunk)) blocks walk their (sample, chunk) items in order, a block's 4 waves
+ *   are summed in wave order, the blocks' partials in ws in block order, and only the real (i, j, c, tap) entries are
+ *   written to the four dw_i; db_i [4] = the column sums of dy, all four given or all four null (as the biases of fwd).
+ *   Because of the zero padding a non-finite activation at depth e + t reaches the columns of a convolution whose own
+ *   kernel does not extend to t (0 * inf is NaN); with finite activations the result is the sum of the real taps only.
+ *   Alignment contract: ldx, ldy, lddy, lddx >= 16 and multiples of 4 floats; the x-side pointers (x, dx), the y-side
+ *   pointers (y, dy) and ws 16-byte aligned; weights and biases need their natural alignment.  ws:
+ *   vc_mhst_conv1_ws_floats(B, l1) / vc_mhst_sconv_ws_floats(B, D) floats, the max over the family's directions
+ *   (negative on bad arguments).  B < 1, l1 < 1, D < 1, a bad leading dimension, a null required operand, a misaligned
+ *   pointer, biases partly null and a workspace that is too small return 1 before any launch. */
+#define VC_MHST_CONV1_CHUNK 4
+#define VC_MHST_CONV1_WAVES 1024
+#define VC_MHST_SCONV_CHUNK 4
+#define VC_MHST_SCONV_BLOCKS 256
 #define VC_MHST_PCONV_CHUNK 4
 #define VC_MHST_CONV3_WAVES 512
 #define VC_MHST_EMBED_PART 1156
@@ -1009,6 +1047,21 @@ VC_API int vc_mhst_pconv_dgrad(int B, int D, int C, int O, int G, int KS, const 
                                float* dx, long lddx, float beta, float* ws, long ws_floats, hipStream_t stream);
 VC_API int vc_mhst_pconv_wgrad(int B, int D, int C, int O, int G, int KS, const float* x, long ldx, const float* dy,
                                long lddy, float* dw, float* db, float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_mhst_conv1_ws_floats(int B, int l1);
+VC_API int vc_mhst_conv1_fwd(int B, int l1, const float* x, const float* w, const float* bias, float* y, long ldy,
+                             float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_mhst_conv1_wgrad(int B, int l1, const float* x, const float* dy, long lddy, float* dw, float* db,
+                               float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_mhst_sconv_ws_floats(int B, int D);
+VC_API int vc_mhst_sconv_fwd(int B, int D, const float* x, long ldx, const float* w1, const float* w2, const float* w3,
+                             const float* w4, const float* b1, const float* b2, const float* b3, const float* b4,
+                             float* y, long ldy, float* ws, long ws_floats, hipStream_t stream);
+VC_API int vc_mhst_sconv_dgrad(int B, int D, const float* dy, long lddy, const float* w1, const float* w2,
+                               const float* w3, const float* w4, float* dx, long lddx, float beta, float* ws,
+                               long ws_floats, hipStream_t stream);
+VC_API int vc_mhst_sconv_wgrad(int B, int D, const float* x, long ldx, const float* dy, long lddy, float* dw1,
+                               float* dw2, float* dw3, float* dw4, float* db1, float* db2, float* db3, float* db4,
+                               float* ws, long ws_floats, hipStream_t stream);
 VC_API int vc_mhst_embed_fwd(int B, const float* ph, const float* pl, const float* wh, const float* wl, const float* W,
                              const float* bias, const float* pos, const float* cls, float* xcnn, float* X0,
                              hipStream_t stream);

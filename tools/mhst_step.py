@@ -5,10 +5,13 @@ device-side seed), the kernel launches per step and the five largest kernels of 
 device time (torch.profiler, a separate pass); then the 3x3x3 convolution's three MFMA kernels and the direct form of its
 forward alone (HIP events), and every pyramidal site kind the MFMA family accepts (`vc_mhst_pconv_ok`) in each of the
 three directions on both families, `vc_mhst_conv_*` and `vc_mhst_pconv_*`, with nominal and issued MFLOP per patch and
-the fraction of the fp32 MFMA peak (157.3 TFLOP/s).  `--conv direct|mfma|both` chooses the model's conv mode for the step
-timings; `both` times the two modes in one process, their samples interleaved (A, B, A, B, ...), as the two families'
-always are.  DESIGN.md section 28 records the output.
-usage: python tools/mhst_step.py [K] [--no-profile] [--conv direct|mfma|both]"""
+the fraction of the fp32 MFMA peak (157.3 TFLOP/s); then the front of the HSI encoder the same way: `hsi conv1`
+(`vc_mhst_conv_*` against `vc_mhst_conv1_*`) and `hsi spectral` (the direct family's four launches together against the
+one fused `vc_mhst_sconv_*` launch).  `--conv direct|mfma|mfma_all|both` chooses the model's conv mode for the step
+timings; `both` times the three modes in one process, their samples interleaved (A, B, C, A, B, C, ...), as the
+families' always are.  DESIGN.md section 28 records the output (profiles/mhst_pconv_step.log, and with the third mode
+profiles/mhst_sconv_step.log).
+usage: python tools/mhst_step.py [K] [--no-profile] [--conv direct|mfma|mfma_all|both]"""
 import os
 import statistics
 import sys
@@ -212,6 +215,92 @@ def pconv_sites(l1, k, fixed_sites):
                   f"{verdict}", flush=True)
 
 
+def verdict_line(l1, name, direction, direct, new, nominal, issued):
+    (dm, dlo, dhi), (mm, mlo, mhi) = direct, new
+    verdict = "mfma wholly below direct" if mhi < dlo else "RANGES OVERLAP" if mlo <= dhi else "direct below mfma"
+    print(f"  {l1} bands {name} {direction}: direct median {dm:.4f} ms (min {dlo:.4f}, max {dhi:.4f}), mfma "
+          f"median {mm:.4f} ms (min {mlo:.4f}, max {mhi:.4f}), {nominal:.2f} MFLOP/patch nominal, "
+          f"{issued:.2f} issued, mfma at {100.0 * nominal * 1e6 * B / (mlo * 1e-3) / PEAK_FP32_MFMA:.2f}% "
+          f"of the fp32 MFMA peak (direct {100.0 * nominal * 1e6 * B / (dlo * 1e-3) / PEAK_FP32_MFMA:.2f}%): "
+          f"{verdict}", flush=True)
+
+
+SPECTRAL_TAPS = (1, 3, 5, 11)
+CONV1_CHUNK = 4                  # VC_MHST_CONV1_CHUNK
+
+
+def front_sites(l1, k):
+    """hsi_encoder.conv1 and the four spectral convolutions, each direction, the direct family (the spectral site: its
+    four launches together, as the program issues them) and the MFMA families interleaved; issued MFLOP by
+    csrc/mhst_sconv.hip's own loop structure"""
+    from vitcnn_amd._lib import lib
+    L = lib()
+    dev = torch.device("cuda", 0)
+    s = torch.cuda.current_stream(dev).cuda_stream
+    D1 = (l1 + 2) // 3
+    M3 = B * D1 * 64
+    P = lambda t: t.data_ptr()   # noqa: E731
+    # conv1: fwd issues 27 steps for each of the chunk's depths (a last chunk that is not full included), wgrad 7 tap
+    # tiles per k-step of 4 positions
+    x1 = torch.rand(B, l1, 8, 8, device=dev)
+    w1, b1, dw1, db1 = (torch.rand(n, device=dev) - 0.5 for n in (16 * 99, 16, 16 * 99, 16))
+    y, dy = torch.empty(M3, 16, device=dev), torch.rand(M3, 16, device=dev)
+    n1 = L.vc_mhst_conv1_ws_floats(B, l1)
+    ws1 = torch.empty(n1, device=dev)
+    d1 = (l1, 8, 8, 1, 16, 1, 11, 3, 3, 5, D1)
+    pairs = {
+        "fwd": (lambda: L.vc_mhst_conv_fwd(B, *d1, P(x1), 1, P(w1), P(b1), P(y), 16, s),
+                lambda: L.vc_mhst_conv1_fwd(B, l1, P(x1), P(w1), P(b1), P(y), 16, P(ws1), n1, s)),
+        "wgrad": (lambda: L.vc_mhst_conv_wgrad(B, *d1, P(x1), 1, P(dy), 16, P(dw1), P(db1), s),
+                  lambda: L.vc_mhst_conv1_wgrad(B, l1, P(x1), P(dy), 16, P(dw1), P(db1), P(ws1), n1, s)),
+    }
+    nominal = 2.0 * D1 * 64 * 16 * 99 / 1e6
+    chunks = (D1 + CONV1_CHUNK - 1) // CONV1_CHUNK
+    issued = {"fwd": chunks * CONV1_CHUNK * 4 * 27 * MFMA_FLOP / 1e6, "wgrad": D1 * 16 * 7 * MFMA_FLOP / 1e6}
+    for direction, fns in pairs.items():
+        for fn in fns:
+            for _ in range(3):
+                fn()
+        direct, new = timed_ab(fns, k)
+        verdict_line(l1, f"hsi conv1 D1={D1}", direction, direct, new, nominal, issued[direction])
+    # spectral: a (depth, offset) pair inside the cube costs 16 MFMAs per plane in every direction
+    x, dx = torch.rand(M3, 16, device=dev), torch.zeros(M3, 16, device=dev)
+    ws_, bs_ = [torch.rand(64 * t, device=dev) - 0.5 for t in SPECTRAL_TAPS], [torch.rand(4, device=dev) for _ in SPECTRAL_TAPS]
+    dws, dbs = [torch.empty(64 * t, device=dev) for t in SPECTRAL_TAPS], [torch.empty(4, device=dev) for _ in SPECTRAL_TAPS]
+    n2 = L.vc_mhst_sconv_ws_floats(B, D1)
+    ws2 = torch.empty(n2, device=dev)
+    shp = [(D1, 8, 8, 16, 4, 1, t, 1, 1, t // 2, D1) for t in SPECTRAL_TAPS]
+
+    def direct_fwd():
+        for i in range(4):
+            L.vc_mhst_conv_fwd(B, *shp[i], P(x), 16, P(ws_[i]), P(bs_[i]), P(y) + 16 * i, 16, s)
+
+    def direct_dgrad():
+        for i in range(4):
+            L.vc_mhst_conv_dgrad(B, *shp[i], P(dy) + 16 * i, 16, P(ws_[i]), P(dx), 16, 1.0 if i else 0.0, s)
+
+    def direct_wgrad():
+        for i in range(4):
+            L.vc_mhst_conv_wgrad(B, *shp[i], P(x), 16, P(dy) + 16 * i, 16, P(dws[i]), P(dbs[i]), s)
+
+    wp, bp = [P(t) for t in ws_], [P(t) for t in bs_]
+    pairs = {
+        "fwd": (direct_fwd, lambda: L.vc_mhst_sconv_fwd(B, D1, P(x), 16, *wp, *bp, P(y), 16, P(ws2), n2, s)),
+        "dgrad": (direct_dgrad, lambda: L.vc_mhst_sconv_dgrad(B, D1, P(dy), 16, *wp, P(dx), 16, 0.0, P(ws2), n2, s)),
+        "wgrad": (direct_wgrad, lambda: L.vc_mhst_sconv_wgrad(B, D1, P(x), 16, P(dy), 16, *(P(t) for t in dws),
+                                                              *(P(t) for t in dbs), P(ws2), n2, s)),
+    }
+    nominal = 2.0 * D1 * 64 * 16 * 4 * sum(SPECTRAL_TAPS) / 1e6
+    inside = sum(1 for e in range(D1) for t in range(-5, 6) if 0 <= e + t < D1)
+    issued = inside * 16 * MFMA_FLOP / 1e6
+    for direction, fns in pairs.items():
+        for fn in fns:
+            for _ in range(3):
+                fn()
+        direct, new = timed_ab(fns, k)
+        verdict_line(l1, f"hsi spectral D={D1} (direct: 4 launches)", direction, direct, new, nominal, issued)
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--") or a == "--conv"]
     conv = "direct"
@@ -219,13 +308,14 @@ def main():
         i = args.index("--conv")
         conv = args[i + 1]
         del args[i:i + 2]
-    if conv not in ("direct", "mfma", "both"):
-        raise SystemExit("--conv takes direct, mfma or both")
+    if conv not in ("direct", "mfma", "mfma_all", "both"):
+        raise SystemExit("--conv takes direct, mfma, mfma_all or both")
     k = int(args[0]) if args else 30
     for l1 in (144, 30):
-        run(l1, k, "--no-profile" not in sys.argv, ("direct", "mfma") if conv == "both" else (conv,))
+        run(l1, k, "--no-profile" not in sys.argv, ("direct", "mfma", "mfma_all") if conv == "both" else (conv,))
         conv_alone(l1, k)
         pconv_sites(l1, k, fixed_sites=l1 == 144)
+        front_sites(l1, k)
 
 
 if __name__ == "__main__":

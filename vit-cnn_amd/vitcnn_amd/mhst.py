@@ -29,7 +29,10 @@ Gumbel draws) from the caller instead; the program keeps what it used in `noise`
 default and the recorded program, or "mfma": every pyramidal site whose shape `vc_mhst_pconv_ok` accepts
 (`hsi_encoder.conv4`, `lidar_encoder.conv2`, `pyconv_classifier.conv1`) runs forward, data and weight gradient through
 `vc_mhst_pconv_*`, exact-fp32 implicit GEMMs on the MFMA, in train, eval and `test()`; the strided
-`hsi_encoder.conv1`, the spectral convs and `lidar_encoder.conv1` stay on `vc_mhst_conv_*`.
+`hsi_encoder.conv1`, the spectral convs and `lidar_encoder.conv1` stay on `vc_mhst_conv_*`.  "mfma_all" is "mfma" plus the
+front of the HSI encoder on the MFMA: `hsi_encoder.conv1` through `vc_mhst_conv1_fwd / _wgrad` and the four spectral
+convolutions as one convolution, `vc_mhst_sconv_fwd` forward and one `vc_mhst_sconv_wgrad` then one `vc_mhst_sconv_dgrad`
+backward; only `lidar_encoder.conv1` (1 to 3 input channels) stays on `vc_mhst_conv_*`.
 
 The patch side is 8 (`encoder_embedding` is Linear(16, 64) and `PoolAttention.hw_shape` (8, 8)); any HSI and LiDAR
 band count >= 1.
@@ -245,9 +248,10 @@ class MHST(FlatParams, nn.Module):
         _check_packed(self)
 
     def set_conv(self, conv: str):
-        """The family behind the pyramidal convolutions: "direct" (`vc_mhst_conv_*`) or "mfma" (`vc_mhst_pconv_*` at every
-        site whose shape `vc_mhst_pconv_ok` accepts).  Every forward builds its program from the current value; a
-        TrainStepper's captured graphs are bound to the mode they recorded and are dropped when it changes."""
+        """The family behind the convolutions: "direct" (`vc_mhst_conv_*`), "mfma" (`vc_mhst_pconv_*` at every pyramidal
+        site whose shape `vc_mhst_pconv_ok` accepts) or "mfma_all" ("mfma" plus `vc_mhst_conv1_*` at `hsi_encoder.conv1`
+        and `vc_mhst_sconv_*` for the four spectral convolutions).  Every forward builds its program from the current
+        value; a TrainStepper's captured graphs are bound to the mode they recorded and are dropped when it changes."""
         self.conv = _check_conv(conv)
         return self
 
@@ -273,7 +277,7 @@ class MHST(FlatParams, nn.Module):
         return program.run(self, _Program, hsi, lidar, gate_noise)
 
 
-CONV_MODES = ("direct", "mfma")
+CONV_MODES = ("direct", "mfma", "mfma_all")
 
 
 def _check_conv(conv):
@@ -334,9 +338,12 @@ class _Program(program.Program):
         # ONE workspace for the GEMMs' split-K slabs, vc_colsum / BatchNorm partials and the 3x3x3 weight gradient's
         # per-wave partials: every launch of the program is on one stream, in order, and each kernel has consumed its
         # partials when it ends, so no two users overlap.  A second stream would need a workspace of its own.
-        self.mfma = m.conv == "mfma"
+        self.mfma = m.conv in ("mfma", "mfma_all")
+        self.front = m.conv == "mfma_all"   # hsi_encoder.conv1 and the spectral convs on the MFMA too
         pws = max(self.pconv_ws(shp) for kind in self.shapes().values()
                   for shp in (kind if isinstance(kind, list) else [kind])) if self.mfma else 0
+        if self.front:
+            pws = max(pws, self.L.vc_mhst_conv1_ws_floats(self.B, m.l1), self.L.vc_mhst_sconv_ws_floats(self.B, self.D1))
         self.scratch(max(1 << 22, part, self.L.vc_mhst_conv3_wgrad_ws_floats(self.B, self.D1), pws), grow=True)
         self.noise_in = gate_noise
         self.seed_dropout(self.train)
@@ -408,12 +415,21 @@ class _Program(program.Program):
         he, le = m.hsi_encoder, m.lidar_encoder
         # HSI encoder (MHST.py:93-119): x1 [B, l1, 8, 8] is the 3-D rows (b, d, h, w) of one channel
         y1 = self.new(M3, 16)
-        self.conv(sh["h1"], self.x1, 1, "hsi_encoder.conv1.weight", "hsi_encoder.conv1.bias", y1, 0, 16)
+        scr, ns = self.scr.data_ptr(), self.SCRATCH
+        if self.front:
+            L.vc_mhst_conv1_fwd(B, m.l1, self.x1.data_ptr(), P["hsi_encoder.conv1.weight"], P["hsi_encoder.conv1.bias"],
+                                y1.data_ptr(), 16, scr, ns, s)
+        else:
+            self.conv(sh["h1"], self.x1, 1, "hsi_encoder.conv1.weight", "hsi_encoder.conv1.bias", y1, 0, 16)
         z1, mean1, inv1 = self.bn("hsi_encoder.bn1", he.bn1, y1, M3, 16)
         y2 = self.new(M3, 16)
-        for i, shp in enumerate(sh["h2"]):
-            pf = f"hsi_encoder.conv2_{i + 1}"
-            self.conv(shp, z1, 16, pf + ".weight", pf + ".bias", y2, 4 * i, 16)
+        spectral = [f"hsi_encoder.conv2_{i + 1}" for i in range(len(SPECTRAL_TAPS))]
+        if self.front:   # the four spectral convs as one convolution, one launch
+            L.vc_mhst_sconv_fwd(B, D1, z1.data_ptr(), 16, *(P[pf + ".weight"] for pf in spectral),
+                                *(P[pf + ".bias"] for pf in spectral), y2.data_ptr(), 16, scr, ns, s)
+        else:
+            for i, (pf, shp) in enumerate(zip(spectral, sh["h2"])):
+                self.conv(shp, z1, 16, pf + ".weight", pf + ".bias", y2, 4 * i, 16)
         z2, mean2, inv2 = self.bn("hsi_encoder.bn2", he.bn2, y2, M3, 16)
         y3 = self.new(M3, 16)
         L.vc_mhst_conv3_fwd(B, D1, z2.data_ptr(), 16, P["hsi_encoder.conv3.weight"], P["hsi_encoder.conv3.bias"],
@@ -626,11 +642,22 @@ class _Program(program.Program):
         L.vc_mhst_conv3_dgrad(B, D1, dy3.data_ptr(), 16, P["hsi_encoder.conv3.weight"], dz2.data_ptr(), 16, 0.0, s)
         dy2 = self.bn_bwd("hsi_encoder.bn2", dz2, sv["y2"], sv["mean2"], sv["inv2"], M3, 16)
         dz1 = self.new(M3, 16)
-        for i, shp in enumerate(sh["h2"]):
-            pf = f"hsi_encoder.conv2_{i + 1}"
-            self.conv_bwd(shp, sv["z1"], 16, pf + ".weight", pf + ".bias", dy2, 4 * i, 16, dz1, 1.0 if i else 0.0)
+        spectral = [f"hsi_encoder.conv2_{i + 1}" for i in range(len(SPECTRAL_TAPS))]
+        if self.front:
+            L.vc_mhst_sconv_wgrad(B, D1, sv["z1"].data_ptr(), 16, dy2.data_ptr(), 16,
+                                  *(G[pf + ".weight"] for pf in spectral), *(G[pf + ".bias"] for pf in spectral), scr, ns,
+                                  s)
+            L.vc_mhst_sconv_dgrad(B, D1, dy2.data_ptr(), 16, *(P[pf + ".weight"] for pf in spectral), dz1.data_ptr(), 16,
+                                  0.0, scr, ns, s)
+        else:
+            for i, (pf, shp) in enumerate(zip(spectral, sh["h2"])):
+                self.conv_bwd(shp, sv["z1"], 16, pf + ".weight", pf + ".bias", dy2, 4 * i, 16, dz1, 1.0 if i else 0.0)
         dy1 = self.bn_bwd("hsi_encoder.bn1", dz1, sv["y1"], sv["mean1"], sv["inv1"], M3, 16)
-        self.conv_bwd(sh["h1"], self.x1, 1, "hsi_encoder.conv1.weight", "hsi_encoder.conv1.bias", dy1, 0, 16)
+        if self.front:
+            L.vc_mhst_conv1_wgrad(B, m.l1, self.x1.data_ptr(), dy1.data_ptr(), 16, G["hsi_encoder.conv1.weight"],
+                                  G["hsi_encoder.conv1.bias"], scr, ns, s)
+        else:
+            self.conv_bwd(sh["h1"], self.x1, 1, "hsi_encoder.conv1.weight", "hsi_encoder.conv1.bias", dy1, 0, 16)
         self.sv, self.enc, self.hs = {}, [], []
         return grad
 

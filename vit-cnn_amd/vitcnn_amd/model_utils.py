@@ -283,7 +283,8 @@ def _get_mhst(n_bands, n_bands2, n_classes, device, kwargs):
     0.1, coefficient_hsi 0.6, coefficient_vit 0.7, 8 head-select blocks of 16 heads, tau 5, no qkv bias, mlp_ratio 4),
     AdamW(lr 8e-4), weighted CE over the model's mixture of probabilities, epoch 1000, batch 64; under applyPCA the
     model is built for 30 bands.  `conv="mfma"`: the pyramidal convolutions on the fp32 MFMA (`MHST.set_conv`, DESIGN.md
-    section 28); the default "direct" is the recorded program."""
+    section 28); `conv="mfma_all"`: those plus `hsi_encoder.conv1` and the four spectral convolutions (as one) on the
+    MFMA; the default "direct" is the recorded program."""
     from .mhst import MHST
     kwargs.setdefault("patch_size", 8)
     conv = kwargs.setdefault("conv", "direct")
