@@ -261,6 +261,45 @@ VC_API int vc_conv3x3_tap_wgrad_oihw_ex(int B, int H, int W, int C, int O, int p
 VC_API int vc_conv3x3_tap_dgrad_ex(int B, int H, int W, int C, int O, int pad, const float* dy, long lddy,
                                    const float* wt, float beta, float* dx, long lddx, float* ws, long ws_floats,
                                    int flags, hipStream_t stream);
+/* bf16 operands stored in memory (FusAtNet precision "bf16_store").  The arithmetic contract
+ * is VC_CONV_BF16's -- both operands of each contraction are the RNE bf16 roundings of fp32 values, products
+ * accumulate in fp32; bias add, beta dx, split-K slabs and their fixed-order combine are fp32; zero padding stays
+ * zero; results are run-to-run bit-identical -- but the rounding happens once, where the operand is written, and the
+ * kernels move 2-byte elements through HBM, the DMA ring and LDS with no conversion in the loop (the k order inside an
+ * MFMA differs from VC_CONV_BF16's, so the two are not bit-identical to each other).
+ * A bf16 operand is a matrix of 2-byte elements with a leading dimension ld % 8 == 0 (elements) on a 16-B aligned
+ * base whose columns [C, ld) are zero.
+ *   vc_cast_bf16_2d: dst16 [M][ldd] = RNE bf16 of src [M][C] (ld lds), columns [C, ldd) written 0 (16-B stores).
+ *   vc_conv3x3_pack_bf16_many: vc_conv3x3_pack_many writing Wt16 [O][9][Cw8], Cw8 = C rounded up to 8, padding 0;
+ *     dst16 = host array of n device pointers, each 16-B aligned.
+ *   vc_conv3x3_tap_fwd_h / _wgrad_oihw_h / _dgrad_h: the three implicit GEMMs of the tap-major conv over x16
+ *     (ldx16), dy16 (lddy16) and Wt16, fp32 outputs with the epilogues of vc_conv3x3_tap_fwd / _wgrad_oihw / _dgrad.
+ *     Any C and O; the weight gradient produces no bias gradient (db = vc_colsum_ex of the fp32 dy).
+ * Anything else (ld % 8 != 0, a misaligned or null operand) is status 1 before any launch. */
+VC_API int vc_cast_bf16_2d(long M, int C, const float* src, long lds, void* dst16, long ldd, hipStream_t stream);
+VC_API int vc_conv3x3_pack_bf16_many(int n, const int* shapes, const float* const* src, void* const* dst16,
+                                     hipStream_t stream);
+VC_API int vc_conv3x3_tap_fwd_h(int B, int H, int W, int C, int O, int pad, const void* x16, long ldx16,
+                                const void* wt16, const float* bias, float* y, long ldy, float* ws, long ws_floats,
+                                hipStream_t stream);
+VC_API int vc_conv3x3_tap_wgrad_oihw_h(int B, int H, int W, int C, int O, int pad, const void* x16, long ldx16,
+                                       const void* dy16, long lddy16, float* dw, float* ws, long ws_floats,
+                                       hipStream_t stream);
+VC_API int vc_conv3x3_tap_dgrad_h(int B, int H, int W, int C, int O, int pad, const void* dy16, long lddy16,
+                                  const void* wt16, float beta, float* dx, long lddx, float* ws, long ws_floats,
+                                  hipStream_t stream);
+/* vc_bn_forward_ex / vc_bn_bwd_relu_ex with an optional extra bf16 output (y16 / dx16, ld % 8 == 0 elements, 16-B
+ * aligned; null: exactly the plain call): the RNE bf16 rounding of every value stored to y / dx, bit-equal to
+ * vc_cast_bf16_2d of that fp32 output, columns [C, ld16) written 0.  The fp32 outputs and statistics are bit-equal
+ * to the plain entry points'. */
+VC_API int vc_bn_forward_ex_h(int train, long M, int C, const float* x, long ldx, float eps, float momentum,
+                              float* save_mean, float* save_invstd, float* run_mean, float* run_var, const float* w,
+                              const float* b, int relu, float* y, long ldy, void* y16, long ldy16, float* ws,
+                              long ws_floats, unsigned int* counters, int n_counters, hipStream_t stream);
+VC_API int vc_bn_bwd_relu_ex_h(int train, long M, int C, const float* dy, long lddy, const float* x, long ldx,
+                               const float* mean, const float* invstd, const float* w, const float* b, float* dx,
+                               long lddx, float beta_dx, void* dx16, long lddx16, float* dw, float* db, float beta_w,
+                               float* ws, long ws_floats, unsigned int* counters, int n_counters, hipStream_t stream);
 /* train-mode BatchNorm(x) (statistics as vc_bn_stats_ex: save_* and running stats written) followed by
  * vc_im2col3x3 of the normalised x, the statistics' final reduction done inside the im2col launch
  * (ms_conv_bn_relu's BN -> conv3x3, Mutimodality_Mamba7.py:1035-1048); bit-identical to the two calls. */

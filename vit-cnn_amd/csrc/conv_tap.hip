@@ -818,3 +818,298 @@ VC_EXPORT int vc_conv3x3_tap_dgrad(int B, int H, int W, int C, int O, int pad, c
                                    hipStream_t stream) {
   return vc_conv3x3_tap_dgrad_ex(B, H, W, C, O, pad, dy, lddy, wt, beta, dx, lddx, ws, ws_floats, 0, stream);
 }
+
+// ---- bf16 operands stored in memory (precision "bf16_store"): the operands of conv_pipe's
+// three GEMMs are bf16 matrices -- activations and output gradients as rows of ld % 8 == 0 elements whose columns
+// past C / O are zero (vc_cast_bf16_2d, or the BatchNorm kernels' bf16 outputs), weights as the tap-major arena
+// Wt16 [O][9][Cw8], Cw8 = C rounded up to 8, padding zero (vc_conv3x3_pack_bf16_many).  The rounding happened once,
+// where the operand was written; the kernel only moves 2-byte elements: a 64-wide k-tile is the same 128 B per
+// image row, the same (BM + BN) * 128-B stage and DMA ring as conv_pipe at twice the k, and the fragments go
+// straight from LDS (g2::Stage<true, ...>::frag) into two v_mfma_f32_16x16x32_bf16 per output tile.
+namespace {
+
+__global__ __launch_bounds__(256) void cast_bf16_2d(long M, int C, const float* __restrict__ src, long lds_, uint4* __restrict__ dst,
+                                                    int ld8) {
+  // one thread per 16-B destination chunk (8 columns)
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= M * ld8) return;
+  const long r = e / ld8;
+  const int c = (int)(e - r * ld8) * 8;
+  const float* s = src + r * lds_ + c;
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = c + j < C ? s[j] : 0.f;
+  dst[e] = uint4{g2::pk_bf16(v[0], v[1]), g2::pk_bf16(v[2], v[3]), g2::pk_bf16(v[4], v[5]), g2::pk_bf16(v[6], v[7])};
+}
+
+// conv_pack_many's grid and element map (thread -> (o, c), 9 taps) over the bf16 arena [O][9][Cw8]
+__global__ __launch_bounds__(256) void conv_pack_bf16_many(PackMany P) {
+  const int b = blockIdx.x;
+  int i = 0;
+  for (int k = 1; k < P.n; ++k)
+    if (b >= P.start[k]) i = k;
+  const int O = P.O[i], C = P.C[i], Cw = (C + 7) & ~7;
+  const long e = (long)(b - P.start[i]) * 256 + threadIdx.x;
+  if (e >= (long)O * Cw) return;
+  const int c = (int)(e % Cw), o = (int)(e / Cw);
+  float v[9];
+  const float* s = P.src[i] + ((long)o * C + c) * 9;
+#pragma unroll
+  for (int t = 0; t < 9; ++t) v[t] = c < C ? s[t] : 0.f;
+  unsigned short* d = reinterpret_cast<unsigned short*>(P.dst[i]) + (long)o * 9 * Cw + c;
+#pragma unroll
+  for (int t = 0; t < 9; ++t) d[(long)t * Cw] = (unsigned short)g2::pk_bf16(v[t], 0.f);
+}
+
+// conv_pipe over bf16 operands, 8 waves.  TapArgs as conv_pipe's with x / dy / w pointing at bf16 elements, ldx /
+// lddy in bf16 elements and Cw = Cw8.  The DMA fill realises g2's bf16 images for 16-B pieces of 8 elements; with
+// wave-instruction i (1 KB of an image) and the lane's LDS address 1024 i + 16 lane:
+//   K-contiguous (lds_off): image row 8 i + (lane >> 3), slot lane & 7 holds chunk slot ^ ((row >> 1) & 7), i.e.
+//     k = 8 chunk .. 8 chunk + 7;
+//   row-contiguous (rc_off, ROWS = 64: a k-row is 128 B = four 32-B blocks of 16 columns): k-row 8 i + (lane >> 3),
+//     piece lane & 7 = half (lane & 1) of physical block (lane & 7) >> 1, which holds the columns of block
+//     pb ^ x(k), x(k) = ((k >> 1) & 1) | (((k >> 3) & 1) << 1).
+template <int MODE>
+__global__ __launch_bounds__(512) void conv_pipe_h(TapArgs a, int tn, int nsplit, unsigned total) {
+  constexpr int NW = 8, BM = CP_B, BN = CP_B, WN = NW / 2, NS = 2, KT = 64;
+  constexpr int WTM = BM / 2, WTN = BN / WN, MT = WTM / 16, NT = WTN / 16;
+  constexpr int SA_B = BM * 128, STAGE = (BM + BN) * 128;
+  static_assert(BM / 8 == NW && BN / 8 == NW, "one DMA piece per operand per wave");
+  constexpr bool TA = MODE == WGRAD, TB = MODE != FWD;
+  typedef g2::Stage<true, TA, BM, false> SA;
+  typedef g2::Stage<true, TB, BN, false> SB;
+  __shared__ __attribute__((aligned(1024))) char smem[gp::ring_bytes<BM, BN, NS>()];
+  int zs, xn, ym, zb;
+  const int tm = (a.M + BM - 1) / BM;
+  gp::tile_coords(gp::xcd_linear(blockIdx.x, total), nsplit, tn, tm, 1, zs, xn, ym, zb);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const int m0 = ym * BM;
+  const int ntap = MODE == WGRAD ? xn / a.tpt : 0;
+  const int n0 = MODE == WGRAD ? (xn - ntap * a.tpt) * BN : xn * BN;
+  const int kt0 = zs * a.kper, kt1 = min(a.nk, kt0 + a.kper);
+  const unsigned OOB = gp::OOB;
+  const long in_rows = (long)a.nb * a.H * a.W, out_rows = (long)a.nb * a.OH * a.OW;
+  const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), (short)0,
+                                                    a.x ? (int)(in_rows * a.ldx * 2) : 0, 0x00020000);
+  const auto rdy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), (short)0,
+                                                     a.dy ? (int)(out_rows * a.lddy * 2) : 0, 0x00020000);
+  const auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), (short)0,
+                                                    a.w ? (int)((long)a.O * 9 * a.Cw * 2) : 0, 0x00020000);
+  // this lane's image row / k-row and its chunk coordinates in either image
+  const int rloc = 8 * wave + (lane >> 3);
+  const int kk = 8 * ((lane & 7) ^ ((rloc >> 1) & 7));
+  const int xs = ((rloc >> 1) & 1) | (((rloc >> 3) & 1) << 1);
+  const int col = (((((lane & 7) >> 1) ^ xs)) << 4) + ((lane & 1) << 3);
+  // K-contiguous A (FWD, DGRAD): the gathered row, decomposed once
+  int kb_ = 0, ki_ = 0, kj_ = 0;
+  const bool kok_ = m0 + rloc < a.M;
+  if constexpr (MODE == FWD) split_out(a, kok_ ? m0 + rloc : 0, kb_, ki_, kj_);
+  if constexpr (MODE == DGRAD) split_in(a, kok_ ? m0 + rloc : 0, kb_, ki_, kj_);
+  auto issue = [&](int t) {
+    char* st = smem + (t % NS) * STAGE;
+    const int kt = kt0 + t;
+    unsigned va, vb;
+    if constexpr (MODE == FWD) {
+      const int tap = kt / a.tpt, c = (kt - tap * a.tpt) * KT + kk;
+      const int row = in_row(a, kb_, ki_, kj_, tap);
+      va = (kok_ && row >= 0 && c < a.C) ? (unsigned)(((long)row * a.ldx + c) * 2) : OOB;
+      const int o = n0 + rloc;
+      vb = (o < a.O && c < a.Cw) ? (unsigned)((((long)o * 9 + tap) * a.Cw + c) * 2) : OOB;
+      gp::dma16(rx, st + wave * 1024, va);
+      gp::dma16(rw, st + SA_B + wave * 1024, vb);
+    } else if constexpr (MODE == DGRAD) {
+      const int tap = kt / a.tpt, o0 = (kt - tap * a.tpt) * KT;
+      const int row = out_row(a, kb_, ki_, kj_, tap), o = o0 + kk;
+      va = (kok_ && row >= 0 && o < a.O) ? (unsigned)(((long)row * a.lddy + o) * 2) : OOB;
+      const int ob = o0 + rloc, c = n0 + col;
+      vb = (ob < a.O && c < a.Cw) ? (unsigned)((((long)ob * 9 + tap) * a.Cw + c) * 2) : OOB;
+      gp::dma16(rdy, st + wave * 1024, va);
+      gp::dma16(rw, st + SA_B + wave * 1024, vb);
+    } else {
+      const int p = kt * KT + rloc, o = m0 + col, c = n0 + col;
+      va = (p < a.P && o < a.O) ? (unsigned)(((long)p * a.lddy + o) * 2) : OOB;
+      int row = -1;
+      if (p < a.P) {
+        int b, y, x;
+        split_out(a, p, b, y, x);
+        row = in_row(a, b, y, x, ntap);
+      }
+      vb = (row >= 0 && c < a.C) ? (unsigned)(((long)row * a.ldx + c) * 2) : OOB;
+      gp::dma16(rdy, st + wave * 1024, va);
+      gp::dma16(rx, st + SA_B + wave * 1024, vb);
+    }
+  };
+  f32x4 acc[1][MT][NT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[0][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int nk = kt1 > kt0 ? kt1 - kt0 : 0;   // block-uniform: every lane runs the transposed reads (EXEC all ones)
+  if (nk > 0) issue(0);
+  for (int t = 0; t < nk; ++t) {
+    gp::vm_wait<0>();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of the slot refilled below
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (t + 1 < nk) issue(t + 1);
+    const char* cur = smem + (t % NS) * STAGE;
+    g2::mma_ktile<true, MT, NT, SA, SB, 1>(cur, cur + SA_B, wm * WTM, wn * WTN, lane, acc);
+  }
+  const bool split = nsplit > 1;
+  // C/D map of the 16x16 MFMAs: col = lane & 15, row = (lane >> 4) * 4 + r
+#pragma unroll
+  for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NT; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + wm * WTM + mi * 16 + (lane >> 4) * 4 + r;
+        const int nl = n0 + wn * WTN + ni * 16 + (lane & 15);
+        const int nmax = MODE == FWD ? a.O : a.C;
+        if (m >= a.M || nl >= nmax) continue;
+        const float v = acc[0][mi][ni][r];
+        const int cc = MODE == WGRAD ? ntap * a.C + nl : nl;
+        if (split) {
+          a.part[((long)zs * a.M + m) * a.N + cc] = v;
+        } else if (MODE == WGRAD && a.oihw) {
+          a.out[((long)m * a.C + nl) * 9 + ntap] = v;
+        } else {
+          float* o = a.out + (long)m * a.ldo + cc;
+          if (MODE == FWD) *o = v + (a.bias ? a.bias[cc] : 0.f);
+          else if (MODE == DGRAD) *o = (a.beta != 0.f ? a.beta * *o : 0.f) + v;
+          else *o = v;
+        }
+      }
+}
+
+// launch_conv_pipe's plan with 64-wide k-tiles: the same tile thresholds and the same least k per slice (two
+// k-tiles of 64 for its four of 32); fixed per shape, so a result is run-to-run bit-identical
+template <int MODE>
+int launch_conv_pipe_h(TapArgs& a, int grid_n, float* ws, long ws_floats, hipStream_t stream) {
+  const int tm = vc_cdiv(a.M, CP_B);
+  const long tiles = (long)grid_n * tm;
+  static const long below_[3] = {512, 1024, 512};
+  const long below = below_[MODE];
+  int nsplit = 1;
+  if (ws && tiles < below)
+    nsplit = (int)std::max<long>(1, std::min<long>(std::min<long>((4 * below + tiles - 1) / tiles, a.nk / 2), 64));
+  while (nsplit > 1 && (long)nsplit * a.M * a.N > ws_floats) --nsplit;
+  a.kper = vc_cdiv(a.nk, nsplit);
+  nsplit = vc_cdiv(a.nk, a.kper);
+  a.part = nsplit > 1 ? ws : nullptr;
+  const long total = tiles * nsplit;
+  VC_REQUIRE(total < (1L << 31));
+  hipLaunchKernelGGL(conv_pipe_h<MODE>, dim3((unsigned)total), dim3(512), 0, stream, a, grid_n, nsplit,
+                     (unsigned)total);
+  VC_CHECK_LAUNCH();
+  if (nsplit > 1) {
+    const long n = (long)a.M * a.N;
+    const int vec = (n % 4 == 0) && ((uintptr_t)ws % 16 == 0);
+    hipLaunchKernelGGL(conv_tap_reduce<MODE>, dim3(vc_cdiv(vec ? n / 4 : n, 256)), dim3(256), 0, stream, a, nsplit,
+                       vec);
+    VC_CHECK_LAUNCH();
+  }
+  return VC_OK;
+}
+
+// a bf16 operand the DMA can gather: rows of whole 16-B chunks from a 16-B aligned base
+bool h_ok(const void* p, long ld, long need) { return p && ((uintptr_t)p % 16) == 0 && ld % 8 == 0 && ld >= need; }
+
+}  // namespace
+
+VC_EXPORT int vc_cast_bf16_2d(long M, int C, const float* src, long lds, void* dst16, long ldd, hipStream_t stream) {
+  VC_REQUIRE(M >= 0 && C > 0 && src && lds >= C && h_ok(dst16, ldd, C));
+  if (M == 0) return VC_OK;
+  const long n = M * (ldd / 8);
+  VC_REQUIRE(n < (1L << 31) * 256);
+  hipLaunchKernelGGL(cast_bf16_2d, dim3((unsigned)vc_cdiv(n, 256)), dim3(256), 0, stream, M, C, src, lds,
+                     reinterpret_cast<uint4*>(dst16), (int)(ldd / 8));
+  VC_CHECK_LAUNCH();
+  return VC_OK;
+}
+
+VC_EXPORT int vc_conv3x3_pack_bf16_many(int n, const int* shapes, const float* const* src, void* const* dst16,
+                                        hipStream_t stream) {
+  VC_REQUIRE(n >= 0 && (n == 0 || (shapes && src && dst16)));
+  for (int i0 = 0; i0 < n; i0 += PACK_MAX) {   // PACK_MAX convs per launch
+    PackMany P;
+    P.n = std::min(PACK_MAX, n - i0);
+    long total = 0;
+    for (int k = 0; k < P.n; ++k) {
+      const int O = shapes[2 * (i0 + k)], C = shapes[2 * (i0 + k) + 1];
+      VC_REQUIRE(O > 0 && C > 0 && src[i0 + k] && dst16[i0 + k] && ((uintptr_t)dst16[i0 + k] % 16) == 0);
+      P.O[k] = O;
+      P.C[k] = C;
+      P.src[k] = src[i0 + k];
+      P.dst[k] = reinterpret_cast<float*>(dst16[i0 + k]);
+      P.start[k] = (int)total;
+      total += vc_cdiv((long)O * ((C + 7) & ~7), 256);
+      VC_REQUIRE(total < (1L << 31));
+    }
+    P.start[P.n] = (int)total;
+    hipLaunchKernelGGL(conv_pack_bf16_many, dim3((unsigned)total), dim3(256), 0, stream, P);
+    VC_CHECK_LAUNCH();
+  }
+  return VC_OK;
+}
+
+VC_EXPORT int vc_conv3x3_tap_fwd_h(int B, int H, int W, int C, int O, int pad, const void* x16, long ldx16,
+                                   const void* wt16, const float* bias, float* y, long ldy, float* ws, long ws_floats,
+                                   hipStream_t stream) {
+  VC_REQUIRE(B > 0 && H >= 3 - 2 * pad && W >= 3 - 2 * pad && C > 0 && O > 0 && (pad == 0 || pad == 1));
+  VC_REQUIRE(y && ldy >= O && h_ok(x16, ldx16, C) && h_ok(wt16, 8, 0));
+  TapArgs a = geo(B, H, W, C, O, pad);
+  a.Cw = (C + 7) & ~7;
+  a.M = B * a.OH * a.OW;
+  a.N = O;
+  VC_REQUIRE_I32((long)B * H * W * ldx16 * 2);
+  VC_REQUIRE_I32((long)O * 9 * a.Cw * 2);
+  VC_REQUIRE_I32((long)a.M * ldy);
+  a.tpt = vc_cdiv(C, 64);
+  a.nk = 9 * a.tpt;
+  a.x = reinterpret_cast<const float*>(x16); a.ldx = ldx16;
+  a.w = reinterpret_cast<const float*>(wt16); a.bias = bias; a.out = y; a.ldo = ldy;
+  return launch_conv_pipe_h<FWD>(a, vc_cdiv(O, CP_B), ws, ws_floats, stream);
+}
+
+VC_EXPORT int vc_conv3x3_tap_wgrad_oihw_h(int B, int H, int W, int C, int O, int pad, const void* x16, long ldx16,
+                                          const void* dy16, long lddy16, float* dw, float* ws, long ws_floats,
+                                          hipStream_t stream) {
+  VC_REQUIRE(B > 0 && H >= 3 - 2 * pad && W >= 3 - 2 * pad && C > 0 && O > 0 && (pad == 0 || pad == 1));
+  VC_REQUIRE(dw && h_ok(x16, ldx16, C) && h_ok(dy16, lddy16, O));
+  TapArgs a = geo(B, H, W, C, O, pad);
+  a.Cw = (C + 7) & ~7;
+  a.M = O;
+  a.N = 9 * C;
+  a.P = B * a.OH * a.OW;
+  VC_REQUIRE_I32((long)B * H * W * ldx16 * 2);
+  VC_REQUIRE_I32((long)a.P * lddy16 * 2);
+  VC_REQUIRE_I32((long)O * 9 * C);
+  a.tpt = vc_cdiv(C, CP_B);   // n-tiles per tap
+  a.nk = vc_cdiv(a.P, 64);
+  a.x = reinterpret_cast<const float*>(x16); a.ldx = ldx16;
+  a.dy = reinterpret_cast<const float*>(dy16); a.lddy = lddy16;
+  a.out = dw; a.ldo = 9L * C;
+  a.oihw = 1;
+  return launch_conv_pipe_h<WGRAD>(a, 9 * a.tpt, ws, ws_floats, stream);
+}
+
+VC_EXPORT int vc_conv3x3_tap_dgrad_h(int B, int H, int W, int C, int O, int pad, const void* dy16, long lddy16,
+                                     const void* wt16, float beta, float* dx, long lddx, float* ws, long ws_floats,
+                                     hipStream_t stream) {
+  VC_REQUIRE(B > 0 && H >= 3 - 2 * pad && W >= 3 - 2 * pad && C > 0 && O > 0 && (pad == 0 || pad == 1));
+  VC_REQUIRE(dx && lddx >= C && h_ok(dy16, lddy16, O) && h_ok(wt16, 8, 0));
+  TapArgs a = geo(B, H, W, C, O, pad);
+  a.Cw = (C + 7) & ~7;
+  a.M = B * H * W;
+  a.N = C;
+  VC_REQUIRE_I32((long)a.M * lddx);
+  VC_REQUIRE_I32((long)B * a.OH * a.OW * lddy16 * 2);
+  VC_REQUIRE_I32((long)O * 9 * a.Cw * 2);
+  a.tpt = vc_cdiv(O, 64);
+  a.nk = 9 * a.tpt;
+  a.dy = reinterpret_cast<const float*>(dy16); a.lddy = lddy16;
+  a.w = reinterpret_cast<const float*>(wt16); a.out = dx; a.ldo = lddx; a.beta = beta;
+  return launch_conv_pipe_h<DGRAD>(a, vc_cdiv(C, CP_B), ws, ws_floats, stream);
+}

@@ -8,6 +8,7 @@
 // all rows (B*H*W) and updates running_var with the unbiased one; eval mode uses the
 // running statistics.  Reductions are deterministic (fixed-order partials + Chan merge).
 #include "common.h"
+#include "mfma_tiles.h"
 
 namespace {
 
@@ -179,6 +180,15 @@ __device__ __forceinline__ void bn_dx_store(float* p, float beta_dx, float v) {
 // The ReLU after a BatchNorm, for its backward: the decisions read from the forward's output (out, ld),
 // or recomputed from x and the affine (w, b) with bn_fwd_elem -- the forward's own arithmetic on the same
 // saved statistics, so the same decisions without reading the output; neither: no ReLU
+// the RNE bf16 rounding of v (v_cvt_pk_bf16_f32, the rounding of vc_cast_bf16_2d)
+__device__ __forceinline__ unsigned short bf16_bits(float v) { return (unsigned short)g2::pk_bf16(v, 0.f); }
+
+// columns [C, ld16) of rows [r0, r1) of a bf16 output written 0 by the whole block
+__device__ __forceinline__ void bn_zero_pad16(unsigned short* __restrict__ y16, long ld16, int C, long r0, long r1) {
+  const int pw = (int)(ld16 - C);
+  for (long i = threadIdx.x; i < (r1 - r0) * pw; i += blockDim.x) y16[(r0 + i / pw) * ld16 + C + i % pw] = 0;
+}
+
 struct ReluSrc {
   const float* out;
   long ld;
@@ -276,10 +286,12 @@ __device__ __forceinline__ void bn_stats_reduce(int P, int C, long M, const floa
 }
 
 // y = relu?((x - mean) * invstd * w + b) over rows [r0, r1) of channel c (row lane rl)
-template <int NL = BN_RL>   // row lanes of the block (rl in [0, NL))
+// H: every stored value also goes, rounded RNE to bf16, to y16 (ld ld16)
+template <int NL = BN_RL, bool H = false>   // row lanes of the block (rl in [0, NL))
 __device__ __forceinline__ void bn_apply_rows(const float* __restrict__ x, long ldx, float mf, float isf, float wc,
                                               float bc, int relu, float* __restrict__ y, long ldy, long r0, long r1,
-                                              int c, int rl) {
+                                              int c, int rl, unsigned short* __restrict__ y16 = nullptr,
+                                              long ld16 = 0) {
   for (long rb = r0 + rl; rb < r1; rb += NL * NB) {   // NB rows' loads in flight
     float xv[NB];
 #pragma unroll
@@ -290,6 +302,7 @@ __device__ __forceinline__ void bn_apply_rows(const float* __restrict__ x, long 
         float v = bn_fwd_elem(xv[i], mf, isf, wc, bc);
         if (relu) v = fmaxf(v, 0.f);
         y[(rb + NL * i) * ldy + c] = v;
+        if constexpr (H) y16[(rb + NL * i) * ld16 + c] = bf16_bits(v);
       }
   }
 }
@@ -316,6 +329,28 @@ __global__ __launch_bounds__(BN_T) void bn_apply_stats(int M, int C, const float
                      run_var, blockIdx.y == 0 && rl == 0);
   const long r0 = (long)blockIdx.y * rows_per_block;
   bn_apply_rows(x, ldx, mf, isf, w[c], b[c], relu, y, ldy, r0, min((long)M, r0 + rows_per_block), c, rl);
+}
+
+// bn_apply_stats that also writes the bf16 copy y16 (ld ld16, columns [C, ld16) zero)
+__global__ __launch_bounds__(BN_T) void bn_apply_stats_h(int M, int C, const float* __restrict__ x, long ldx, int P,
+                                                        const double* __restrict__ part, float eps, float momentum,
+                                                        float* __restrict__ save_mean, float* __restrict__ save_invstd,
+                                                        float* __restrict__ run_mean, float* __restrict__ run_var,
+                                                        const float* __restrict__ w, const float* __restrict__ b,
+                                                        int relu, float* __restrict__ y, long ldy, int rows_per_block,
+                                                        const float* __restrict__ shift,
+                                                        unsigned short* __restrict__ y16, long ld16) {
+  __shared__ double tot[2][64];
+  bn_part_sums(P, C, part, blockIdx.x, tot);
+  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl;
+  const long r0 = (long)blockIdx.y * rows_per_block, r1 = min((long)M, r0 + rows_per_block);
+  if (blockIdx.x == gridDim.x - 1) bn_zero_pad16(y16, ld16, C, r0, r1);
+  if (c >= C) return;
+  float mf, isf;
+  bn_stats_from_sums(tot[0][cl], tot[1][cl], c, M, shift, eps, momentum, mf, isf, save_mean, save_invstd, run_mean,
+                     run_var, blockIdx.y == 0 && rl == 0);
+  bn_apply_rows<BN_RL, true>(x, ldx, mf, isf, w[c], b[c], relu, y, ldy, r0, r1, c, rl, y16, ld16);
 }
 
 // partial block (channel group blockIdx.x, rows [blockIdx.y * rows_per, ...)) of the statistics:
@@ -401,6 +436,22 @@ __global__ void bn_apply(int total, FastDiv fC, const float* __restrict__ x, lon
   float v = bn_fwd_elem(x[r * ldx + c], mean[c], invstd[c], w[c], b[c]);
   if (relu) v = fmaxf(v, 0.f);
   y[r * ldy + c] = v;
+}
+
+// bn_apply that also writes the bf16 copy y16; the thread of a row's last channel zeroes the row's padding
+__global__ void bn_apply_h(int total, FastDiv fC, const float* __restrict__ x, long ldx, const float* __restrict__ mean,
+                           const float* __restrict__ invstd, const float* __restrict__ w, const float* __restrict__ b,
+                           int relu, float* __restrict__ y, long ldy, unsigned short* __restrict__ y16, long ld16) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  int c;
+  const long r = fdivmod(idx, fC, c);
+  float v = bn_fwd_elem(x[r * ldx + c], mean[c], invstd[c], w[c], b[c]);
+  if (relu) v = fmaxf(v, 0.f);
+  y[r * ldy + c] = v;
+  y16[r * ld16 + c] = bf16_bits(v);
+  if (c == fC.div - 1)
+    for (long k = fC.div; k < ld16; ++k) y16[r * ld16 + k] = 0;
 }
 
 // BN backward sums: s1 = sum dyv, s2 = sum dyv*xhat (dyv = dy * (relu_out > 0) if relu_out) in fp64.
@@ -497,11 +548,12 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_final(int P, int C, const double*
 }
 
 // dx rows [r0, r1) of channel c (row lane rl) from the channel's sums s1, s2 (train) -- or w*invstd*dyv (eval)
-template <int NL = BN_RL>   // row lanes of the block (rl in [0, NL))
+template <int NL = BN_RL, bool H = false>   // row lanes of the block (rl in [0, NL)); H: as bn_apply_rows
 __device__ __forceinline__ void bn_bwd_apply_rows(int train, int M, const float* __restrict__ dy, long lddy,
                                                   const float* __restrict__ x, long ldx, ReluSrc rs, float mu, float is,
                                                   float wc, double s1, double s2, float* __restrict__ dx, long lddx,
-                                                  float beta_dx, long r0, long r1, int c, int rl) {
+                                                  float beta_dx, long r0, long r1, int c, int rl,
+                                                  unsigned short* __restrict__ dx16 = nullptr, long ld16 = 0) {
   const float invM = 1.f / (float)M;
   const float rw = rs.b ? rs.w[c] : 0.f, rbc = rs.b ? rs.b[c] : 0.f;
   const bool need_x = train || rs.b;
@@ -525,6 +577,7 @@ __device__ __forceinline__ void bn_bwd_apply_rows(int train, int M, const float*
         if (train) v = bn_bwd_elem(d, xv[i], mu, is, wc, (float)s1 * invM, (float)s2 * invM);
         else v = (wc * is) * d;
         bn_dx_store(dx + (rb + NL * i) * lddx + c, beta_dx, v);
+        if constexpr (H) dx16[(rb + NL * i) * ld16 + c] = bf16_bits(dx[(rb + NL * i) * lddx + c]);
       }
   }
 }
@@ -554,6 +607,32 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_apply_sums(int train, int M, int 
   const long r0 = (long)blockIdx.y * rows_per_block;
   bn_bwd_apply_rows(train, M, dy, lddy, x, ldx, rs, mean[c], invstd[c], w[c], s1, s2, dx, lddx, beta_dx, r0,
                     min((long)M, r0 + rows_per_block), c, rl);
+}
+
+// bn_bwd_apply_sums that also writes the bf16 copy dx16 of the stored dx (ld ld16, columns [C, ld16) zero)
+__global__ __launch_bounds__(BN_T) void bn_bwd_apply_sums_h(int train, int M, int C, const float* __restrict__ dy,
+                                                           long lddy, const float* __restrict__ x, long ldx,
+                                                           ReluSrc rs, const float* __restrict__ mean,
+                                                           const float* __restrict__ invstd,
+                                                           const float* __restrict__ w, int P,
+                                                           const double* __restrict__ part, float* __restrict__ dx,
+                                                           long lddx, float beta_dx, float* __restrict__ dw,
+                                                           float* __restrict__ db, float beta_w, int rows_per_block,
+                                                           unsigned short* __restrict__ dx16, long ld16) {
+  __shared__ double tot[2][64];
+  bn_part_sums(P, C, part, blockIdx.x, tot);
+  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl;
+  const long r0 = (long)blockIdx.y * rows_per_block, r1 = min((long)M, r0 + rows_per_block);
+  if (blockIdx.x == gridDim.x - 1) bn_zero_pad16(dx16, ld16, C, r0, r1);
+  if (c >= C) return;
+  const double s1 = tot[0][cl], s2 = tot[1][cl];
+  if (blockIdx.y == 0 && rl == 0) {
+    if (dw) dw[c] = (beta_w != 0.f ? beta_w * dw[c] : 0.f) + (float)s2;
+    if (db) db[c] = (beta_w != 0.f ? beta_w * db[c] : 0.f) + (float)s1;
+  }
+  bn_bwd_apply_rows<BN_RL, true>(train, M, dy, lddy, x, ldx, rs, mean[c], invstd[c], w[c], s1, s2, dx, lddx, beta_dx,
+                                 r0, r1, c, rl, dx16, ld16);
 }
 
 // train: dx = w*invstd*(dyv - s1/M - xhat*s2/M);  eval (sums == null): dx = w*invstd*dyv
@@ -887,16 +966,22 @@ VC_EXPORT int vc_bn_forward(int train, long M, int C, const float* x, long ldx, 
                           ldy, ws, ws_floats, nullptr, 0, stream);
 }
 
-VC_EXPORT int vc_bn_forward_ex(int train, long M, int C, const float* x, long ldx, float eps, float momentum,
-                               float* save_mean, float* save_invstd, float* run_mean, float* run_var, const float* w,
-                               const float* b, int relu, float* y, long ldy, float* ws, long ws_floats,
-                               unsigned int* counters, int n_counters, hipStream_t stream) {
+// y16 (nullable; ld16): the bf16 copy of y, written by the _h forms of the two apply kernels
+static int bn_forward_impl(int train, long M, int C, const float* x, long ldx, float eps, float momentum,
+                           float* save_mean, float* save_invstd, float* run_mean, float* run_var, const float* w,
+                           const float* b, int relu, float* y, long ldy, unsigned short* y16, long ld16, float* ws,
+                           long ws_floats, hipStream_t stream) {
   VC_REQUIRE(C > 0 && M >= 0);
   if (!train || M == 0) {
     int rc = vc_bn_stats(train, M, C, x, ldx, eps, momentum, save_mean, save_invstd, run_mean, run_var, ws, ws_floats,
                          stream);
     if (rc) return rc;
-    return vc_bn_apply(M, C, x, ldx, save_mean, save_invstd, w, b, relu, y, ldy, stream);
+    if (!y16 || M == 0) return vc_bn_apply(M, C, x, ldx, save_mean, save_invstd, w, b, relu, y, ldy, stream);
+    VC_REQUIRE_I32(M * C);
+    hipLaunchKernelGGL(bn_apply_h, dim3(vc_cdiv(M * C, 256)), dim3(256), 0, stream, (int)(M * C), make_fastdiv(C), x,
+                       ldx, save_mean, save_invstd, w, b, relu, y, ldy, y16, ld16);
+    VC_CHECK_LAUNCH();
+    return VC_OK;
   }
   VC_REQUIRE(M < (1L << 31) && ((uintptr_t)ws & 7) == 0);
   double* wsd = reinterpret_cast<double*>(ws);
@@ -904,16 +989,44 @@ VC_EXPORT int vc_bn_forward_ex(int train, long M, int C, const float* x, long ld
   const int rows_per = bn_rows_per(M, C, ws_doubles, 0);
   const int P = vc_cdiv(M, rows_per);
   VC_REQUIRE((long)P * C * 2 <= ws_doubles && P <= 65535);
-  (void)counters;
-  (void)n_counters;
   hipLaunchKernelGGL(bn_stats_sums, dim3(vc_cdiv(C, 64), P), dim3(BN_T), 0, stream, (int)M, C, x, ldx, rows_per, wsd,
                      (unsigned int*)nullptr, eps, momentum, save_mean, save_invstd, run_mean, run_var);
   VC_CHECK_LAUNCH();
   const int rpb = bn_apply_rows();
-  hipLaunchKernelGGL(bn_apply_stats, dim3(vc_cdiv(C, 64), vc_cdiv(M, rpb)), dim3(BN_T), 0, stream, (int)M, C, x, ldx,
-                     P, wsd, eps, momentum, save_mean, save_invstd, run_mean, run_var, w, b, relu, y, ldy, rpb, x);
+  if (y16)
+    hipLaunchKernelGGL(bn_apply_stats_h, dim3(vc_cdiv(C, 64), vc_cdiv(M, rpb)), dim3(BN_T), 0, stream, (int)M, C, x,
+                       ldx, P, wsd, eps, momentum, save_mean, save_invstd, run_mean, run_var, w, b, relu, y, ldy, rpb,
+                       x, y16, ld16);
+  else
+    hipLaunchKernelGGL(bn_apply_stats, dim3(vc_cdiv(C, 64), vc_cdiv(M, rpb)), dim3(BN_T), 0, stream, (int)M, C, x, ldx,
+                       P, wsd, eps, momentum, save_mean, save_invstd, run_mean, run_var, w, b, relu, y, ldy, rpb, x);
   VC_CHECK_LAUNCH();
   return VC_OK;
+}
+
+// the counters are ignored: the channel-tiled apply reduces the partials itself
+VC_EXPORT int vc_bn_forward_ex(int train, long M, int C, const float* x, long ldx, float eps, float momentum,
+                               float* save_mean, float* save_invstd, float* run_mean, float* run_var, const float* w,
+                               const float* b, int relu, float* y, long ldy, float* ws, long ws_floats,
+                               unsigned int* counters, int n_counters, hipStream_t stream) {
+  (void)counters;
+  (void)n_counters;
+  return bn_forward_impl(train, M, C, x, ldx, eps, momentum, save_mean, save_invstd, run_mean, run_var, w, b, relu, y,
+                         ldy, nullptr, 0, ws, ws_floats, stream);
+}
+
+// a bf16 output: rows of whole 16-B chunks on a 16-B aligned base
+static bool bn_h_ok(const void* p, long ld, int C) { return ((uintptr_t)p % 16) == 0 && ld % 8 == 0 && ld >= C; }
+
+VC_EXPORT int vc_bn_forward_ex_h(int train, long M, int C, const float* x, long ldx, float eps, float momentum,
+                                 float* save_mean, float* save_invstd, float* run_mean, float* run_var, const float* w,
+                                 const float* b, int relu, float* y, long ldy, void* y16, long ldy16, float* ws,
+                                 long ws_floats, unsigned int* counters, int n_counters, hipStream_t stream) {
+  (void)counters;
+  (void)n_counters;
+  VC_REQUIRE(!y16 || bn_h_ok(y16, ldy16, C));
+  return bn_forward_impl(train, M, C, x, ldx, eps, momentum, save_mean, save_invstd, run_mean, run_var, w, b, relu, y,
+                         ldy, static_cast<unsigned short*>(y16), ldy16, ws, ws_floats, stream);
 }
 
 // train-mode BatchNorm forward from fp64 partials another kernel left (vc_gemm_colstats: P = ceil(M / 64) row tiles,
@@ -948,7 +1061,7 @@ VC_EXPORT int vc_bn_apply(long M, int C, const float* x, long ldx, const float* 
 static int bn_bwd_impl(int train, long M, int C, const float* dy, long lddy, const float* x, long ldx, ReluSrc rs,
                        const float* mean, const float* invstd, const float* w, float* dx, long lddx, float beta_dx,
                        float* dw, float* db, float beta_w, float* ws, long ws_floats, unsigned int* counters,
-                       int n_counters, hipStream_t stream) {
+                       int n_counters, hipStream_t stream, unsigned short* dx16 = nullptr, long ld16 = 0) {
   VC_REQUIRE(C > 0 && M > 0 && M < (1L << 31) && ((uintptr_t)ws & 7) == 0);
   // per-row-block partial sums [P][2][C] and the final [2][C] sums are fp64
   double* wsd = reinterpret_cast<double*>(ws);
@@ -959,15 +1072,22 @@ static int bn_bwd_impl(int train, long M, int C, const float* dy, long lddy, con
   double* sums = wsd + (long)P * C * 2;
   // tickets (the last-arriving partial block reduces) only without dx: with dx the channel-tiled apply
   // reduces the partials itself
-  unsigned int* cnt = (!(train && dx) && counters && n_counters >= vc_cdiv(C, 64)) ? counters : nullptr;
+  // (dx16, the bf16 copy of dx: always the channel-tiled apply, which computes eval-mode dx with bn_bwd_apply's
+  // arithmetic and dw / db from the same fixed-order sums)
+  unsigned int* cnt = (!(train && dx) && !dx16 && counters && n_counters >= vc_cdiv(C, 64)) ? counters : nullptr;
   hipLaunchKernelGGL(bn_bwd_sums, dim3(vc_cdiv(C, 64), P), dim3(BN_T), 0, stream, (int)M, C, dy, lddy, x, ldx,
                      rs, mean, invstd, rows_per, wsd, cnt, sums, dw, db, beta_w);
   VC_CHECK_LAUNCH();
   if (!cnt && dx) {   // the channel-tiled apply reduces the partials itself: one launch fewer
     const int rpb = bn_apply_rows();
-    hipLaunchKernelGGL(bn_bwd_apply_sums, dim3(vc_cdiv(C, 64), vc_cdiv(M, rpb)), dim3(BN_T), 0, stream, train,
-                       (int)M, C, dy, lddy, x, ldx, rs, mean, invstd, w, P, wsd, dx, lddx, beta_dx, dw,
-                       db, beta_w, rpb);
+    if (dx16)
+      hipLaunchKernelGGL(bn_bwd_apply_sums_h, dim3(vc_cdiv(C, 64), vc_cdiv(M, rpb)), dim3(BN_T), 0, stream, train,
+                         (int)M, C, dy, lddy, x, ldx, rs, mean, invstd, w, P, wsd, dx, lddx, beta_dx, dw, db, beta_w,
+                         rpb, dx16, ld16);
+    else
+      hipLaunchKernelGGL(bn_bwd_apply_sums, dim3(vc_cdiv(C, 64), vc_cdiv(M, rpb)), dim3(BN_T), 0, stream, train,
+                         (int)M, C, dy, lddy, x, ldx, rs, mean, invstd, w, P, wsd, dx, lddx, beta_dx, dw,
+                         db, beta_w, rpb);
     VC_CHECK_LAUNCH();
     return VC_OK;
   }
@@ -1002,6 +1122,17 @@ VC_EXPORT int vc_bn_bwd_relu_ex(int train, long M, int C, const float* dy, long 
   VC_REQUIRE(w && b);
   return bn_bwd_impl(train, M, C, dy, lddy, x, ldx, ReluSrc{nullptr, 0, w, b}, mean, invstd, w, dx, lddx, beta_dx,
                      dw, db, beta_w, ws, ws_floats, counters, n_counters, stream);
+}
+
+VC_EXPORT int vc_bn_bwd_relu_ex_h(int train, long M, int C, const float* dy, long lddy, const float* x, long ldx,
+                                  const float* mean, const float* invstd, const float* w, const float* b, float* dx,
+                                  long lddx, float beta_dx, void* dx16, long lddx16, float* dw, float* db, float beta_w,
+                                  float* ws, long ws_floats, unsigned int* counters, int n_counters,
+                                  hipStream_t stream) {
+  VC_REQUIRE(w && b && (!dx16 || (dx && bn_h_ok(dx16, lddx16, C))));
+  return bn_bwd_impl(train, M, C, dy, lddy, x, ldx, ReluSrc{nullptr, 0, w, b}, mean, invstd, w, dx, lddx, beta_dx,
+                     dw, db, beta_w, ws, ws_floats, counters, n_counters, stream, static_cast<unsigned short*>(dx16),
+                     lddx16);
 }
 
 VC_EXPORT int vc_bn_bwd(int train, long M, int C, const float* dy, long lddy, const float* x, long ldx,

@@ -26,6 +26,11 @@ Precision: `FusAtNet(..., precision="bf16")` / `set_preci
 three contractions with both operands rounded RNE to bf16 and fp32 accumulation (`vc_conv3x3_tap_*_ex` with
 `VC_CONV_BF16`); master weights, the bias adds and bias gradients, BatchNorm, Adam and all elementwise work stay fp32,
 and so does `cm.conv6`, the 1x1 head (a plain GEMM, < 0.1 % of the step).  "fp32", the default, is the parity mode.
+`precision="bf16_store"` is the same arithmetic contract with the rounding moved to where an
+operand is written: every 3x3 conv reads bf16 copies of its input, of its output gradient and of the tap-major weights
+(`vc_conv3x3_tap_*_h`), left by the BatchNorm kernels next to their fp32 outputs (`vc_bn_forward_ex_h`,
+`vc_bn_bwd_relu_ex_h`), by `vc_cast_bf16_2d` for the other inputs and by `vc_conv3x3_pack_bf16_many`; the bias gradient
+is `vc_colsum_ex` of the fp32 output gradient.
 """
 from __future__ import annotations
 
@@ -37,7 +42,8 @@ import torch.nn as nn
 from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
-from .model import _IMPLICIT_CONV, N_COUNTERS, _check_precision
+from .model import _IMPLICIT_CONV, N_COUNTERS
+from .model import PRECISIONS as _MODEL_PRECISIONS
 
 # 3x3 convs: the tap-major implicit GEMM (vc_conv3x3_tap_*, conv_tap.hip); False restores the im2col +
 # vc_gemm formulation of rounds 1-2 (a module constant: tools/knobs.py sets it from VITCNN_FUSAT_IM2COL=1)
@@ -48,6 +54,17 @@ _PAD_LIDAR = True
 
 BN_EPS = 1e-5
 CONV_BF16 = 2   # VC_CONV_BF16 (include/vitcnn.h): bf16 operands, fp32 accumulation
+PRECISIONS = _MODEL_PRECISIONS + ("bf16_store",)   # FusAtNet's own: ViT-CNN has no "bf16_store"
+
+
+def _check_precision(p):
+    if p not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {p!r}")
+    return p
+
+
+def _up8(n):
+    return (n + 7) // 8 * 8
 _counters = program.counters   # the pool's old name and home, kept importable
 
 
@@ -158,7 +175,8 @@ class FusAtNet(FlatParams, nn.Module):
 
     `precision` (keyword only; the positional signature and the state_dict are the reference's): "fp32", the parity
     mode, or "bf16": the operands of every 3x3 conv contraction (forward, weight and data gradient) rounded to bf16,
-    fp32 accumulation; `cm.conv6`, the 1x1 head, stays an fp32 GEMM."""
+    fp32 accumulation; `cm.conv6`, the 1x1 head, stays an fp32 GEMM; or "bf16_store": the same contract with the
+    operands rounded once, where they are written, and read as bf16 by the convs."""
 
     def __init__(self, input_channels, input_channels2, num_classes, *, precision="fp32"):
         super().__init__()
@@ -173,8 +191,9 @@ class FusAtNet(FlatParams, nn.Module):
         self._build_flat()
 
     def set_precision(self, precision: str):
-        """Arithmetic of the 3x3 convs: "fp32" (the parity mode) or "bf16" (bf16 operands, fp32 accumulation; master
-        weights, BatchNorm, Adam, the 1x1 head and all elementwise work stay fp32).  Every forward builds its program
+        """Arithmetic of the 3x3 convs: "fp32" (the parity mode), "bf16" (bf16 operands, fp32 accumulation; master
+        weights, BatchNorm, Adam, the 1x1 head and all elementwise work stay fp32) or "bf16_store" (that contract over
+        bf16 copies of the operands kept in memory).  Every forward builds its program
         from the current value; a TrainStepper's captured graphs are bound to the precision they recorded and are
         dropped when it changes."""
         self.precision = _check_precision(precision)
@@ -209,9 +228,12 @@ class _Program(program.Program):
         self.Pp = x1.shape[2]
         self.x1, self.x2 = x1, x2
         self.conv_flags = CONV_BF16 if m.precision == "bf16" else 0
-        if self.conv_flags and not _TAP_CONV:
-            raise RuntimeError("FusAtNet precision='bf16' needs the tap-major convs: the im2col / implicit-GEMM "
-                               "measurement routes are fp32 only")
+        self.h = m.precision == "bf16_store"   # the convs read bf16 copies of their operands
+        if (self.conv_flags or self.h) and not _TAP_CONV:
+            raise RuntimeError(f"FusAtNet precision='{m.precision}' (bf16 operands) needs the tap-major convs: the "
+                               "im2col / implicit-GEMM measurement routes are fp32 only")
+        self.h16 = {}         # id(activation) -> (its bf16 copy, ld, the activation): what a conv reads in "bf16_store"
+        self.g16 = {}         # id(conv output) -> (bf16 copy of its gradient, ld), left by the BatchNorm backward
         self.scratch(max(1 << 22, self.B * self.SCRATCH_PER_SAMPLE))
         self.grad = grad
         self.tape = []        # backward closures, run in reverse
@@ -264,6 +286,18 @@ class _Program(program.Program):
         self.no_grad_ids.add(id(y))
         return y
 
+    def half(self, x, M, C, ldx):
+        """(bf16 copy, ld) of the rows x (M x C, ld ldx), rows of C rounded up to 8 elements with zero padding: the
+        one the BatchNorm forward left (bn_relu), else made here once by vc_cast_bf16_2d and shared by every conv
+        that reads x (the two NHWC inputs, residual sums, pooled maps, the concat)"""
+        got = self.h16.get(id(x))
+        if got is None:
+            ld = _up8(C)
+            t = torch.empty(M, ld, dtype=torch.bfloat16, device=self.dev)
+            self.L.vc_cast_bf16_2d(M, C, x.data_ptr(), ldx, t.data_ptr(), ld, self.s)
+            got = self.h16[id(x)] = (t, ld, x)   # x held: its id stays its own while the entry lives
+        return got[0], got[1]
+
     def conv3(self, x, ldx, H, C, conv, pad):
         """x [B,H,W,C] rows (ld ldx) -> conv3x3 + bias, [B,OH,OH,O] contiguous.
 
@@ -279,8 +313,15 @@ class _Program(program.Program):
         M, K = B * OH * OH, C * 9
         L, scr, flags = self.L, self.scr.data_ptr(), self.conv_flags
         y = self.new(B, OH, OH, O)
-        wt = None
-        if _TAP_CONV:
+        wt = x16 = wt16 = None
+        ld16 = 0
+        if self.h:   # "bf16_store": bf16 x and Wt (pack_all's bf16 arena), fp32 bias add and output
+            wt = self.wts[id(conv)]
+            wt16 = self.wts16[id(conv)]
+            x16, ld16 = self.half(x, B * H * H, C, ldx)
+            L.vc_conv3x3_tap_fwd_h(B, H, H, C, O, pad, x16.data_ptr(), ld16, wt16.data_ptr(), conv.bias.data_ptr(),
+                                   y.data_ptr(), O, scr, self.SCRATCH, self.s)
+        elif _TAP_CONV:
             wt = self.wts.get(id(conv))   # tap-major weight (rows padded to 4), read again by dgrad
             if wt is None:
                 wt = self.new(O * 9 * ((C + 3) // 4 * 4))
@@ -299,6 +340,17 @@ class _Program(program.Program):
 
         def bwd():
             dy = self.grad_of(y)
+            if self.h:   # the forward's x16 again; dy16 from the BatchNorm backward (else cast); db = colsum(fp32 dy)
+                dy16, ldd = self.g16.pop(id(y), None) or self.half(dy, M, O, O)
+                L.vc_conv3x3_tap_wgrad_oihw_h(B, H, H, C, O, pad, x16.data_ptr(), ld16, dy16.data_ptr(), ldd,
+                                              self.pgrad(conv.weight), scr, self.SCRATCH, self.s)
+                L.vc_colsum_ex(M, O, dy.data_ptr(), O, self.pgrad(conv.bias), 0.0, scr, self.SCRATCH, self.cnt,
+                               N_COUNTERS, self.s)
+                if id(x) not in self.no_grad_ids:
+                    gx, beta = self.acc(x)
+                    L.vc_conv3x3_tap_dgrad_h(B, H, H, C, O, pad, dy16.data_ptr(), ldd, wt16.data_ptr(), beta,
+                                             gx.data_ptr(), ldx, scr, self.SCRATCH, self.s)
+                return
             if _TAP_CONV:   # weight gradient in the torch layout and the bias gradient, by the wgrad launch
                 L.vc_conv3x3_tap_wgrad_oihw_ex(B, H, H, C, O, pad, x.data_ptr(), ldx, dy.data_ptr(), O,
                                                self.pgrad(conv.weight), self.pgrad(conv.bias), scr, self.SCRATCH,
@@ -328,17 +380,35 @@ class _Program(program.Program):
         self.record(bwd, x, y) if wt is None else self.record(bwd, x, y, wt)
         return y, OH
 
-    def bn_relu(self, y, M, C, bn, relu=1):
+    def bn_relu(self, y, M, C, bn, relu=1, to_conv=False):
+        """to_conv: z is the input of a 3x3 conv, so in "bf16_store" the apply also writes z's bf16 copy; and there the
+        backward leaves the bf16 copy of y's gradient for the conv that produced y"""
         mean, invstd = self.new(C), self.new(C)
         z = self.new(*y.shape) if self.grad else y
+        ld16 = _up8(C)
+        z16 = torch.empty(M, ld16, dtype=torch.bfloat16, device=self.dev) if self.h and to_conv else None
         # train: statistics partials + the channel-tiled apply that reduces them (two launches)
-        self.L.vc_bn_forward_ex(1 if self.train else 0, M, C, y.data_ptr(), C, bn.eps, self.bn_momentum(bn),
-                                mean.data_ptr(), invstd.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                bn.weight.data_ptr(), bn.bias.data_ptr(), relu, z.data_ptr(), C, self.scr.data_ptr(),
-                                self.SCRATCH, self.cnt, N_COUNTERS, self.s)
+        args = (1 if self.train else 0, M, C, y.data_ptr(), C, bn.eps, self.bn_momentum(bn), mean.data_ptr(),
+                invstd.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.weight.data_ptr(),
+                bn.bias.data_ptr(), relu, z.data_ptr(), C)
+        tail = (self.scr.data_ptr(), self.SCRATCH, self.cnt, N_COUNTERS, self.s)
+        if z16 is None:
+            self.L.vc_bn_forward_ex(*args, *tail)
+        else:
+            self.L.vc_bn_forward_ex_h(*args, z16.data_ptr(), ld16, *tail)
+            self.h16[id(z)] = (z16, ld16, z)
 
         def bwd():
             gy, beta = self.acc(y)
+            if relu and self.h:
+                gy16 = torch.empty(M, ld16, dtype=torch.bfloat16, device=self.dev)
+                self.L.vc_bn_bwd_relu_ex_h(1 if self.train else 0, M, C, self.grad_of(z).data_ptr(), C, y.data_ptr(),
+                                           C, mean.data_ptr(), invstd.data_ptr(), bn.weight.data_ptr(),
+                                           bn.bias.data_ptr(), gy.data_ptr(), C, beta, gy16.data_ptr(), ld16,
+                                           self.pgrad(bn.weight), self.pgrad(bn.bias), 0.0, self.scr.data_ptr(),
+                                           self.SCRATCH, self.cnt, N_COUNTERS, self.s)
+                self.g16[id(y)] = (gy16, ld16)
+                return
             if relu:   # the ReLU decisions recomputed from y and the affine: z is not read again
                 self.L.vc_bn_bwd_relu_ex(1 if self.train else 0, M, C, self.grad_of(z).data_ptr(), C, y.data_ptr(), C,
                                          mean.data_ptr(), invstd.data_ptr(), bn.weight.data_ptr(),
@@ -359,15 +429,15 @@ class _Program(program.Program):
         """address of p's slice of the flat gradient (every parameter is written once, beta 0)"""
         return self.gflat.data_ptr() + F32 * self.poff[id(p)]
 
-    def unit(self, x, ldx, H, C, u, pad=1):
+    def unit(self, x, ldx, H, C, u, pad=1, to_conv=True):
         y, OH = self.conv3(x, ldx, H, C, u.conv, pad)
-        return self.bn_relu(y, self.B * OH * OH, u.conv.out_channels, u.bn), OH
+        return self.bn_relu(y, self.B * OH * OH, u.conv.out_channels, u.bn, to_conv=to_conv), OH
 
     def residual(self, x, ldx, H, C, r, pool):
         a, _ = self.conv3(x, ldx, H, C, r.conv1, 1)
         O = r.conv1.out_channels
         M = self.B * H * H
-        a = self.bn_relu(a, M, O, r.bn1)
+        a = self.bn_relu(a, M, O, r.bn1, to_conv=True)
         b, _ = self.conv3(a, O, H, O, r.conv2, 1)
         b = self.bn_relu(b, M, O, r.bn2)
         out = self.new(*b.shape) if self.grad else b
@@ -420,7 +490,7 @@ class _Program(program.Program):
 
     def six(self, x, ldx, H, C, mod):
         for u in (mod.conv1, mod.conv2, mod.conv3, mod.conv4, mod.conv5, mod.conv6):
-            x, _ = self.unit(x, ldx, H, C, u)
+            x, _ = self.unit(x, ldx, H, C, u, to_conv=u is not mod.conv6)
             C = ldx = u.conv.out_channels
         return x
 
@@ -428,12 +498,13 @@ class _Program(program.Program):
         x, _ = self.residual(x, ldx, H, C, mod.res1, False)
         x, _ = self.residual(x, 128, H, 128, mod.res2, False)
         x, _ = self.unit(x, 256, H, 256, mod.conv1)
-        x, _ = self.unit(x, 256, H, 256, mod.conv2)
+        x, _ = self.unit(x, 256, H, 256, mod.conv2, to_conv=False)
         return x
 
     def pack_all(self):
-        """every 3x3 conv's tap-major weights in one arena, packed by one launch (vc_conv3x3_pack_many)"""
-        self.wts = {}
+        """every 3x3 conv's tap-major weights in one arena, packed by one launch (vc_conv3x3_pack_many); in
+        "bf16_store" also the bf16 arena [O][9][C rounded up to 8] the convs read (vc_conv3x3_pack_bf16_many)"""
+        self.wts, self.wts16 = {}, {}
         if not _TAP_CONV:
             return
         convs = [c for c in self.m.modules() if isinstance(c, nn.Conv2d) and tuple(c.kernel_size) == (3, 3)]
@@ -451,6 +522,17 @@ class _Program(program.Program):
             off += k
         self.L.vc_conv3x3_pack_many(n, ctypes.addressof(shapes), ctypes.addressof(src), ctypes.addressof(dst),
                                     self.s)
+        if not self.h:
+            return
+        sizes = [c.out_channels * 9 * _up8(c.in_channels) for c in convs]   # multiples of 8: 16-B aligned slices
+        arena16 = torch.empty(sum(sizes), dtype=torch.bfloat16, device=self.dev)
+        off = 0
+        for i, (c, k) in enumerate(zip(convs, sizes)):
+            self.wts16[id(c)] = arena16[off:off + k]
+            dst[i] = arena16.data_ptr() + 2 * off
+            off += k
+        self.L.vc_conv3x3_pack_bf16_many(n, ctypes.addressof(shapes), ctypes.addressof(src), ctypes.addressof(dst),
+                                         self.s)
 
     def _forward(self):
         m, L, B, P = self.m, self.L, self.B, self.Pp
@@ -466,7 +548,7 @@ class _Program(program.Program):
         t, H = self.residual(x1, c1, P, c1, sa.res1, True)
         t, H = self.residual(t, 256, H, 256, sa.res2, True)
         t, _ = self.unit(t, 256, H, 256, sa.conv1)
-        t, _ = self.unit(t, 256, H, 256, sa.conv2)
+        t, _ = self.unit(t, 256, H, 256, sa.conv2, to_conv=False)
         t = self.maxpool(t, H, 1024)
         Hp = H // 2
         Ct = c1 + c2 + 2048
@@ -500,7 +582,7 @@ class _Program(program.Program):
         self.keep[id(Fss)] = Fss
         x, H, C = Fss, P, 1024
         for u in (m.cm.conv1, m.cm.conv2, m.cm.conv3, m.cm.conv4, m.cm.conv5):
-            x, H = self.unit(x, C, H, C, u, pad=0)
+            x, H = self.unit(x, C, H, C, u, pad=0, to_conv=u is not m.cm.conv5)
             C = u.conv.out_channels
         Mo = B * H * H
         logits = self.new(Mo, m.ncls)
@@ -530,5 +612,5 @@ class _Program(program.Program):
                   beta=beta)
         for fn in reversed(self.tape):
             fn()
-        self.tape, self.g, self.keep = [], {}, {}
+        self.tape, self.g, self.keep, self.h16, self.g16 = [], {}, {}, {}, {}
         return self.gflat

@@ -1,6 +1,6 @@
 """Run the reference's own CLI (`main.py`) on the MI355X path, single-GPU or data parallel under torchrun.
 
-    python -m vitcnn_amd.launch --main /path/to/reference/main.py [--precision fp32|bf16] -- <main.py args>
+    python -m vitcnn_amd.launch --main /path/to/reference/main.py [--precision fp32|bf16|bf16_store] -- <main.py args>
     torchrun --nnodes 1 --nproc-per-node 8 --master-addr 127.0.0.1 -m vitcnn_amd.launch \
         --main /path/to/reference/main.py -- --model Multimodality_Mamba --dataset Houston2013 ...
 
@@ -44,9 +44,10 @@ _EDITS = [
      "    filename = filename.replace('.txt', '.rank' + os.environ['RANK'] + '.txt')\n"
      "sys.stdout = open(filename, 'w')"),
     ("args = parser.parse_args()",
-     "parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16'],\n"
+     "parser.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'bf16', 'bf16_store'],\n"
      "                    help='operand precision of the MI355X path: ViT-CNN GEMMs and FusAtNet 3x3 convs '\n"
-     "                         '(bf16: bf16 operands, fp32 accumulation); other models are fp32 only')\n"
+     "                         '(bf16: bf16 operands, fp32 accumulation; bf16_store: FusAtNet only, '\n"
+     "                         'the operands kept as bf16 in memory); other models are fp32 only')\n"
      "args = parser.parse_args()\n"
      "_VC_RANK, _VC_WORLD, _VC_LOCAL = _vc_parallel.init_from_env()"),
     ("CUDA_DEVICE = get_device(args.cuda)",
@@ -78,7 +79,7 @@ def main(argv=None):
         argv, rest = argv[:i], argv[i + 1:]
     ap = argparse.ArgumentParser(prog="python -m vitcnn_amd.launch")
     ap.add_argument("--main", required=True, help="path of the reference's main.py")
-    ap.add_argument("--precision", choices=("fp32", "bf16"), default=None,
+    ap.add_argument("--precision", choices=("fp32", "bf16", "bf16_store"), default=None,
                     help="shorthand for main.py's added --precision")
     a = ap.parse_args(argv)
     path = os.path.abspath(a.main)

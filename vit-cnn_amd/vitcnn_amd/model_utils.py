@@ -29,7 +29,8 @@ each rank iterates its own shard of the batches (a loader that is not already sh
 
 Precision (BASELINE.json config 2): `get_model(..., precision="bf16")` builds ViT-CNN with bf16
 GEMM operands and fp32 accumulation (`Multimodality_Mamba.set_precision`), and FusAtNet with bf16 operands on
-its 3x3 convolutions (`FusAtNet.set_precision`); the default "fp32" is the parity mode.
+its 3x3 convolutions (`FusAtNet.set_precision`; FusAtNet alone also takes "bf16_store", the same
+contract over operands kept as bf16 in memory, section 30); the default "fp32" is the parity mode.
 The other models have no bf16 mode.
 """
 from __future__ import annotations
@@ -152,7 +153,8 @@ def _get_fusatnet(n_bands, n_bands2, n_classes, device, kwargs):
     parameter buffer (torch.optim.Adam's update exactly) --, weighted CE, epoch 150, batch 64, applyPCA False.
     The reference's backward raises (in-place residual add); this path trains with
     out-of-place residual semantics (vitcnn_amd/fusatnet.py).  `precision="bf16"`: bf16 operands on the 3x3 convs
-    (`FusAtNet.set_precision`)."""
+    (`FusAtNet.set_precision`); `precision="bf16_store"`: those operands stored as bf16
+    (section 30)."""
     from .fusatnet import FusAtNet
     kwargs.setdefault("patch_size", 11)
     precision = kwargs.setdefault("precision", "fp32")
