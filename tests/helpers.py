@@ -105,6 +105,68 @@ def launch_trace(L):
             setattr(L, name, fn)
 
 
+class LaneRecorder:
+    """The ViT-CNN step's lane DAG through `vitcnn_amd.model._TRACER` (wrap / mark / wait): every library call of the
+    program as [entry point, [its non-pointer arguments, as launch_trace takes them], lane, [the indices of the calls
+    it depends on: the lane's previous call and the calls the events it waited for follow]].  Free of addresses."""
+
+    def __init__(self):
+        self.nodes = []
+        self.last = {}      # lane -> index of its latest call
+        self.pending = {}   # lane -> calls behind the events it waited for since its latest call
+        self.marks = {}     # id(event) -> the calls the event follows
+
+    def wrap(self, L, prog):
+        return _Recorded(L, prog, self)
+
+    def _front(self, lane):
+        return self.pending.get(lane, set()) | ({self.last[lane]} if lane in self.last else set())
+
+    def mark(self, e, lane):
+        self.marks[id(e)] = self._front(lane)
+
+    def wait(self, e, lane):
+        self.pending.setdefault(lane, set()).update(self.marks.get(id(e), ()))
+
+    def call(self, name, args, lane):
+        self.nodes.append([name, args, lane, sorted(self._front(lane))])
+        self.pending.pop(lane, None)
+        self.last[lane] = len(self.nodes) - 1
+
+
+class _Recorded:
+    """the bound library as a program sees it under a LaneRecorder (size queries and predicates pass through)"""
+
+    def __init__(self, L, prog, rec):
+        self._L, self._prog, self._rec = L, prog, rec
+
+    def __getattr__(self, name):
+        import ctypes
+        fn = getattr(self._L, name)
+        if not name.startswith("vc_") or name.endswith(("_floats", "_ok")):
+            return fn
+        kinds = [None if t is ctypes.c_void_p else float if t in (ctypes.c_float, ctypes.c_double) else int
+                 for t in self._L.sigs[name]]
+
+        def call(*args):
+            self._rec.call(name, [k(a) for k, a in zip(kinds, args) if k is not None], self._prog.cur)
+            return fn(*args)
+
+        return call
+
+
+@contextlib.contextmanager
+def lane_trace():
+    """the LaneRecorder of every ViT-CNN program built inside the block"""
+    import vitcnn_amd.model as VM
+    rec, saved = LaneRecorder(), VM._TRACER
+    VM._TRACER = rec
+    try:
+        yield rec
+    finally:
+        VM._TRACER = saved
+
+
 def load_case(name, cache):
     """A comparison model's fixture (tests/golden/<name>.npz and its <name>_p*.npz / <name>_g*.npz parts): {"keys",
     "state" (initial state_dict, fp32), "grads" (the float64 twin's), "running" (BatchNorm running statistics and

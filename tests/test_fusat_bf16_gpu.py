@@ -211,7 +211,7 @@ def test_precision_change_drops_the_captured_graph(runs):
 
 
 def test_measurement_routes_refuse_bf16(runs, monkeypatch):
-    """im2col + vc_gemm and the element-gather implicit GEMM are fp32 only: bf16 raises at program build, fp32 runs"""
+    """the im2col + vc_gemm measurement route is fp32 only: bf16 raises at program build, fp32 runs"""
     from vitcnn_amd import fusatnet
     monkeypatch.setattr(fusatnet, "_TAP_CONV", False)
     x1, x2 = runs["x1"][:2].to(DEV), runs["x2"][:2].to(DEV)

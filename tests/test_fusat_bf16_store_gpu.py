@@ -195,7 +195,7 @@ def test_other_modes_are_untouched_by_a_bf16_store_forward(runs):
 
 
 def test_measurement_routes_refuse_bf16_store(runs, monkeypatch):
-    """im2col + vc_gemm and the element-gather implicit GEMM are fp32 only: the mode raises at program build"""
+    """the im2col + vc_gemm measurement route is fp32 only: the mode raises at program build"""
     from vitcnn_amd import fusatnet
     monkeypatch.setattr(fusatnet, "_TAP_CONV", False)
     m = _seeded(MODE).to(DEV).train()

@@ -1,9 +1,9 @@
 """Measurement switches for the tools: VITCNN_<NAME> environment variables -> the program's module constants.
 
-The product package reads no environment (vitcnn_amd/model.py, fusatnet.py: module constants with the
-measured-fastest defaults; the C ABI's kernel knobs exist only in libvitcnn_probe.so).  A tool that A/Bs
-a switch (tools/ab_env.sh -> prof_step.py) imports this module first: it selects the probe library
-and copies every VITCNN_* switch that is set onto the corresponding constant.
+The product package reads no environment (vitcnn_amd/model.py, fusatnet.py: module constants, the lane schedule
+family and FusAtNet's im2col route; the C ABI's kernel knobs exist only in libvitcnn_probe.so).  A tool that A/Bs
+a switch (tools/ab_env.sh -> prof_step.py) imports this module first: it selects the probe library, copies every
+VITCNN_* switch that is set onto the corresponding constant, and refuses a retired one.
 """
 import os
 import sys
@@ -36,33 +36,27 @@ if "VITCNN_LIB" in os.environ or any(k in os.environ for k in PROBE_KNOBS):
 # env name -> (module, attribute, parser)
 _FLAG = lambda v: v not in ("0", "", "false", "False")  # noqa: E731
 SWITCHES = {
-    "VITCNN_IMPLICIT_CONV": ("model", "_IMPLICIT_CONV", _FLAG),
-    "VITCNN_DEFER_WGRAD": ("model", "_DEFER_WGRAD", _FLAG),
-    "VITCNN_DEFER_WGRAD1": ("model", "_DEFER_WGRAD1", _FLAG),
-    "VITCNN_SCAN_FUSED": ("model", "_SCAN_FUSED", _FLAG),
-    "VITCNN_ROW_CHAIN": ("model", "_ROW_CHAIN", _FLAG),
-    "VITCNN_GLF_FUSED": ("model", "_GLF_FUSED", _FLAG),
-    "VITCNN_ONE_PARAM_REDUCE": ("model", "_ONE_PARAM_REDUCE", _FLAG),
-    "VITCNN_TAP_DGRAD": ("model", "_TAP_DGRAD", _FLAG),
     "VITCNN_LANES": ("model", "_LANES", _FLAG),
     "VITCNN_LANES_BWD": ("model", "_LANES_BWD", _FLAG),
-    "VITCNN_GEMM_GROUP": ("model", "_GROUP", _FLAG),
-    "VITCNN_BF16_MIN_K": ("model", "_BF16_MIN_K", int),
-    "VITCNN_GLOBAL_FIRST": ("model", "_GLOBAL_FIRST", _FLAG),
     "VITCNN_LANE_MAP": ("model", "_LANE_MAP", lambda v: [int(x) for x in v.split(",") if x]),
-    "VITCNN_BN_TICKETS": ("model", "_BN_TICKETS", _FLAG),
-    "VITCNN_BN_RELU_AFFINE": ("model", "_BN_RELU_AFFINE", _FLAG),
     "VITCNN_CH_LANE": ("model", "_CH_LANE", int),
     "VITCNN_CH_ORDERED": ("model", "_CH_ORDERED", _FLAG),
     "VITCNN_FUSAT_IM2COL": ("fusatnet", "_TAP_CONV", lambda v: not _FLAG(v)),
-    "VITCNN_FUSAT_PAD_LIDAR": ("fusatnet", "_PAD_LIDAR", _FLAG),
-    "VITCNN_GEMM_BNSTATS": ("model", "_GEMM_BNSTATS", _FLAG),
-    "VITCNN_PG_LANE2": ("model", "_PG_LANE2", _FLAG),
 }
+# switches of program forms that no longer exist ("Retired program forms"): an old A/B command line that
+# sets one would compare two identical legs, so apply() refuses it
+RETIRED = ("VITCNN_IMPLICIT_CONV", "VITCNN_TAP_DGRAD", "VITCNN_DEFER_WGRAD", "VITCNN_DEFER_WGRAD1",
+           "VITCNN_GLOBAL_FIRST", "VITCNN_PG_LANE2", "VITCNN_BN_TICKETS", "VITCNN_BN_RELU_AFFINE",
+           "VITCNN_ONE_PARAM_REDUCE", "VITCNN_BF16_MIN_K", "VITCNN_GEMM_GROUP", "VITCNN_GEMM_BNSTATS",
+           "VITCNN_SCAN_FUSED", "VITCNN_GLF_FUSED", "VITCNN_ROW_CHAIN", "VITCNN_FUSAT_PAD_LIDAR")
 
 
 def apply():
     import importlib
+    gone = [k for k in RETIRED if k in os.environ]
+    if gone:
+        raise RuntimeError(f"{', '.join(gone)}: retired switch, the program has one form now (DESIGN.md, 'Retired "
+                           f"program forms', names the last commit with both)")
     done = {}
     for env, (mod, attr, parse) in SWITCHES.items():
         v = os.environ.get(env)
@@ -71,8 +65,6 @@ def apply():
         m = importlib.import_module("vitcnn_amd." + mod)
         setattr(m, attr, parse(v))
         done[env] = getattr(m, attr)
-    if "VITCNN_IMPLICIT_CONV" in done:   # fusatnet imported the constant by value
-        importlib.import_module("vitcnn_amd.fusatnet")._IMPLICIT_CONV = done["VITCNN_IMPLICIT_CONV"]
     return done
 
 

@@ -42,15 +42,12 @@ import torch.nn as nn
 from . import program
 from ._lib import lib
 from .flat import F32, FlatParams
-from .model import _IMPLICIT_CONV, N_COUNTERS
+from .model import N_COUNTERS
 from .model import PRECISIONS as _MODEL_PRECISIONS
 
 # 3x3 convs: the tap-major implicit GEMM (vc_conv3x3_tap_*, conv_tap.hip); False restores the im2col +
 # vc_gemm formulation of rounds 1-2 (a module constant: tools/knobs.py sets it from VITCNN_FUSAT_IM2COL=1)
 _TAP_CONV = True
-# the LiDAR input (C2 bands, 1 at config 5) laid out in rows padded to 4 floats with zero columns, so its 3x3 convs
-# take the pipelined conv (conv_tap.hip conv_pipe_ok: 16-B rows) instead of conv_tap
-_PAD_LIDAR = True
 
 BN_EPS = 1e-5
 CONV_BF16 = 2   # VC_CONV_BF16 (include/vitcnn.h): bf16 operands, fp32 accumulation
@@ -231,7 +228,7 @@ class _Program(program.Program):
         self.h = m.precision == "bf16_store"   # the convs read bf16 copies of their operands
         if (self.conv_flags or self.h) and not _TAP_CONV:
             raise RuntimeError(f"FusAtNet precision='{m.precision}' (bf16 operands) needs the tap-major convs: the "
-                               "im2col / implicit-GEMM measurement routes are fp32 only")
+                               "im2col measurement route is fp32 only")
         self.h16 = {}         # id(activation) -> (its bf16 copy, ld, the activation): what a conv reads in "bf16_store"
         self.g16 = {}         # id(conv output) -> (bf16 copy of its gradient, ld), left by the BatchNorm backward
         self.scratch(max(1 << 22, self.B * self.SCRATCH_PER_SAMPLE))
@@ -305,9 +302,9 @@ class _Program(program.Program):
         gathered input rows, so neither an im2col matrix (611 MB for the 2193-channel concat) nor a
         col2im pass exists; the weights are repacked tap-major per step (vc_conv3x3_pack, in the
         captured graph) and the tap-major weight gradient unpacked into the flat gradient.
-        VITCNN_FUSAT_IM2COL=1: vc_im2col3x3_pad + vc_gemm (rounds 1-2); VITCNN_IMPLICIT_CONV=1 with it:
-        the element-gather implicit GEMM vc_conv3x3_*.  The model's precision reaches the tap-major route only
-        (`self.conv_flags`, all three directions); the two measurement routes refuse bf16 at program build."""
+        VITCNN_FUSAT_IM2COL=1 (_TAP_CONV = False): vc_im2col3x3_pad + vc_gemm (rounds 1-2).  The model's precision
+        reaches the tap-major route only (`self.conv_flags`, all three directions); the im2col measurement route
+        refuses bf16 at program build."""
         B, O = self.B, conv.out_channels
         OH = H + 2 * pad - 2
         M, K = B * OH * OH, C * 9
@@ -328,9 +325,6 @@ class _Program(program.Program):
                 L.vc_conv3x3_pack(O, C, 0, conv.weight.data_ptr(), wt.data_ptr(), 0.0, self.s)
             L.vc_conv3x3_tap_fwd_ex(B, H, H, C, O, pad, x.data_ptr(), ldx, wt.data_ptr(), conv.bias.data_ptr(),
                                     y.data_ptr(), O, scr, self.SCRATCH, flags, self.s)
-        elif _IMPLICIT_CONV:
-            L.vc_conv3x3_fwd(B, H, H, C, O, pad, x.data_ptr(), ldx, None, None, None, None, conv.weight.data_ptr(),
-                             conv.bias.data_ptr(), 0, y.data_ptr(), O, scr, self.SCRATCH, self.s)
         else:
             col = self.new(M, K)
             L.vc_im2col3x3_pad(B, H, H, C, pad, x.data_ptr(), ldx, col.data_ptr(), self.s)
@@ -359,13 +353,6 @@ class _Program(program.Program):
                     gx, beta = self.acc(x)
                     L.vc_conv3x3_tap_dgrad_ex(B, H, H, C, O, pad, dy.data_ptr(), O, wt.data_ptr(), beta,
                                               gx.data_ptr(), ldx, scr, self.SCRATCH, flags, self.s)
-                return
-            if _IMPLICIT_CONV:
-                L.vc_conv3x3_wgrad(B, H, H, C, O, pad, x.data_ptr(), ldx, None, None, None, None, dy.data_ptr(), O,
-                                   0.0, self.pgrad(conv.weight), self.pgrad(conv.bias), scr, self.SCRATCH, self.s)
-                if id(x) not in self.no_grad_ids:
-                    L.vc_conv3x3_dgrad(B, H, H, C, O, pad, dy.data_ptr(), O, conv.weight.data_ptr(), 1.0,
-                                       self.grad_of(x).data_ptr(), ldx, scr, self.SCRATCH, self.s)
                 return
             colr = self.new(M, K)   # recomputed: cheaper than keeping every im2col matrix
             L.vc_im2col3x3_pad(B, H, H, C, pad, x.data_ptr(), ldx, colr.data_ptr(), self.s)
@@ -538,7 +525,9 @@ class _Program(program.Program):
         m, L, B, P = self.m, self.L, self.B, self.Pp
         self.pack_all()
         c1, c2 = m.c1, m.c2
-        ld2 = (c2 + 3) // 4 * 4 if _PAD_LIDAR else c2
+        # the LiDAR rows (C2 bands, 1 at config 5) padded to 4 floats with zero columns, so its 3x3 convs take the
+        # pipelined conv (conv_tap.hip conv_pipe_ok: 16-B rows) instead of conv_tap
+        ld2 = (c2 + 3) // 4 * 4
         x1, x2 = self.nhwc(self.x1), self.nhwc(self.x2, ld2)
         HW = P * P
         M = B * HW

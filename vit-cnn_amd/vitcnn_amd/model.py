@@ -39,70 +39,25 @@ BN_EPS = 1e-5
 BN_MOM = 0.1
 NDIR = 10
 N_SIDE = 3                 # side streams: 1 = local/non-local branch, 2 = channel branch, 3 = LiDAR branch
-_ONE_PARAM_REDUCE = True   # a hsiMamba block's scan / conv1d parameter gradients in one reduction launch
 WGRAD_LANE = 2             # backward: lane 0's deferred weight gradients (lane 2 is idle after the forward)
-WGRAD1_LANE = 3            # backward: lane 1's deferred weight gradients (lane 3: after the fusion1 / LiDAR chain)
-# Program switches.  Module constants -- the product reads no environment: each selects between two
-# forms the tests hold to the same parity (or bit-identity), and the measurement tools set them from
-# VITCNN_<NAME> variables through tools/knobs.py (tools/ab_env.sh A/B runs).  The defaults are the
-# measured-fastest forms.
-#
-# 3x3 convs of ViT-CNN: im2col + vc_gemm by default; VITCNN_IMPLICIT_CONV=1 selects the implicit GEMM
-# (vc_conv3x3_*), measured slower on this step (2.39 -> 2.55 ms: the per-element gather with the fused
-# BN affine costs more VALU than the small im2col matrices cost bandwidth); FusAtNet, whose col
-# matrices reach 611 MB, always uses the implicit GEMM
-_IMPLICIT_CONV = False
-# lane-0 weight gradients are batched and issued on the weight-gradient lane at a few flush points
-# (one fork each); forking each one separately measured slower (2.39 -> 2.63 ms: every cross-lane
-# graph edge costs more than one GEMM's overlap gains); False: every weight gradient in place
-_DEFER_WGRAD = True
-# lane 1's weight gradients (GLfusion, local conv, channel feature) queued and issued on WGRAD1_LANE at the end
-# of the block's lane-1 chain, so lane 1 -- the critical path since round 3 -- runs the data gradients only.
-# Measured slower: 1.80-1.81 -> 1.99-2.02 ms (profiles/r04_ab_defer_wgrad1.log): the block's grouped weight
-# gradients then run beside lane 0's scan backward and stretch it more than lane 1 gains
-_DEFER_WGRAD1 = False
 SIDE_SCRATCH = 1 << 23     # floats of scratch per side stream
 PARAM_ALIGN = 4            # floats: flat-buffer alignment (16 B) of every parameter of >= ALIGN_MIN elements
 ALIGN_MIN = 64
 GEMM_GROUP_BYTES = 16384   # VC_GEMM_GROUP_BYTES (include/vitcnn.h)
 GEMM_MASK = 64             # vc_gemm flags: the addend is a ReLU mask (include/vitcnn.h)
-# capture order of a GlobalLocal block's forward: lane 0's global view (the hsiMamba chain) captured before the local /
-# channel branches it runs beside (the same DAG, bit-identical).  Measured 1.695 vs 1.687 ms (3 rounds x 300 replays,
-# profiles/r06_ab_global_first.log): kept off
-_GLOBAL_FIRST = False
-# conv1x1 + BatchNorm (+ ReLU) forward: the statistics partials computed in the GEMM epilogue (vc_gemm_colstats)
-_GEMM_BNSTATS = True
-# GLfusion forward: the NonLocal phi | g projection on the channel lane (2) right after ln4, theta alone on lane 1
-_PG_LANE2 = False   # measured slower: 1.745 -> 1.758-1.762 ms (profiles/r05_ab_pg_lane2.log)
 N_COUNTERS = 1 << 16       # split-K tile counters per stream
 
-# the Mamba direction conv + x_proj folded into the scan launch and the dt_proj / x_proj data gradients +
-# conv1d backward into the scan backward's tail (vc_mamba_scan_fwd_fused / _bwd_fused); False restores the
-# separate launches
-_SCAN_FUSED = True
-# patch_embed + pre_norm + in_proj and combine + out_proj + ln1 + change_dim as one launch each
-# (vc_rowchain_front / _back); False restores the separate launches
-_ROW_CHAIN = True
-# GLfusion: the phi | g max pool inside the non-local attention forward and its backward inside the
-# attention backward, the concat gradient's add + copy as one launch (vc_nonlocal_attn_pool_fwd / _bwd,
-# vc_add2_2d_dup); False restores the separate launches
-_GLF_FUSED = True
-# the local conv's data gradient as the tap-major implicit GEMM (vc_conv3x3_tap_dgrad, no dcol matrix, no
-# col2im) over the weights packed tap-major by lane 0 in the forward: opt-in, measured slower on the B=64
-# step (1.90-1.94 -> 1.99-2.01 ms: at 7x7 / 9x9 maps the row gathers cost more than dcol + col2im)
-_TAP_DGRAD = False
+# The step has one program form.  The forms that six rounds of A/B measurement rejected (implicit-GEMM and tap-major
+# 3x3 routes, a second weight-gradient lane, the unfused scan and non-local attention, ...) are gone with their
+# switches; DESIGN.md, "Retired program forms", keeps what each selected, the measurement that decided it and the
+# last commit that has it.  What is left below, module constants (the product reads no environment; the measurement
+# tools set them from VITCNN_<NAME> variables through tools/knobs.py):
+#
+# the lane schedule.  Every setting computes the same bits: tests/test_model_gpu.py::
+# test_lane_schedules_are_bit_identical drives _LANES_BWD, _LANE_MAP, _CH_LANE and _CH_ORDERED, and
+# tests/test_lane_trace_gpu.py pins the default DAG and the one of _LANES_BWD = False.
 _LANES = True        # branch-level stream concurrency (False: every lane on the caller's stream)
-_LANES_BWD = True    # the same for the backward alone
-_TRACER = None   # launch-structure recorder of tools/critical_path.py (None in normal runs)
-_GROUP = True        # grouped launches of independent fp32 GEMMs
-# bf16 mode diagnostics (tools/bf16_sites.py): GEMM issue indices kept in fp32, and a log of call sites
-_BF16_EXACT: set = set()
-# bf16 mode: bf16 operands for products with K >= this that are not weight gradients; 0 = every GEMM
-# bf16 (the reference's autocast mode).  Round 4: with bf16 MFMAs in the pipelined kernel (grouped like the
-# fp32 problems) every GEMM in bf16 is the fastest: 1.67-1.69 vs 1.78 ms/step with 1024 (round 3's value,
-# the im2col'ed 3x3 convs only) on one box, fp32 1.805 (profiles/r04_ab_bf16_min_k.log)
-_BF16_MIN_K = 0
-_GEMM_SITES = None
+_LANES_BWD = True    # the same for the backward alone (False: no deferral, every weight gradient in place)
 _LANE_MAP = []       # logical lane -> stream index (empty: lane i on stream i)
 # the channel-feature backward chain's lane: 1 = after the local-conv chain on lane 1 (default); 3 = on
 # lane 3 beside it (measured slower, round 3: 2.01 -> 2.23 ms).  Both chains accumulate into the block's
@@ -111,9 +66,12 @@ _LANE_MAP = []       # logical lane -> stream index (empty: lane i on stream i)
 # the two read-modify-write GEMM epilogues race, and the result depends on the schedule)
 _CH_LANE = 1
 _CH_ORDERED = True
-_BN_RELU_AFFINE = True   # BN + ReLU backward: the ReLU decisions recomputed from the BN input and affine
-_BN_TICKETS = False  # BN reductions without dx in the last-arriving block: measured ~1% slower (every arrival is an
-#                     agent-scope release = L2 writeback); with dx the counters select the one-launch kernels
+# diagnostics hooks, None / empty in normal runs: the launch-structure recorder (tools/critical_path.py, the tests'
+# helpers.LaneRecorder), and for the bf16 mode (tools/bf16_sites.py) a log of the GEMM call sites and the GEMM issue
+# indices kept in fp32
+_TRACER = None
+_GEMM_SITES = None
+_BF16_EXACT: set = set()
 
 UNUSED_PREFIXES = ("hsi1.global_view.tokenlearner.", "hsi1.global_view.ln3.",
                    "hsi2.global_view.tokenlearner.", "hsi2.global_view.ln3.")
@@ -590,10 +548,6 @@ class _Program:
         self._scr = [(scr.data_ptr(), scr.numel())] + [(t.data_ptr(), t.numel()) for _, t in lanes]
         self._cnt = [t.data_ptr() for t in model._tile_counters(device)]
         self.gemm_flags = GEMM_BF16 if model.precision == "bf16" else 0
-        # 3x3 convs as implicit GEMMs (fp32 only, opt-in); bf16 operands use im2col + the bf16 vc_gemm
-        self.implicit_conv = not self.gemm_flags and _IMPLICIT_CONV
-        self.scan_fused = _SCAN_FUSED
-        self.row_chain = _ROW_CHAIN
         self.cur = 0
         self._gemm_i = 0
         self._ev_i = 0
@@ -601,8 +555,6 @@ class _Program:
         self.lanes_on = _LANES
         self.wgrad_tail = None
         self.pending_wgrads = []
-        self.wgrad_tail1 = None
-        self.pending_wgrads1 = []
         self._grouping = None      # the open GEMM group's state (host address) while gemm_group() collects
         self._group_lane = 0
         _, self.P, self.BUF, self.I64 = model._ptrs()
@@ -634,25 +586,23 @@ class _Program:
         self._ev_i += 1
         return e
 
-    def site_flags(self, ta, M, N, K, exact=False):
+    def site_flags(self, M, N, K, exact=False):
         """one GEMM site of the program: its index (the _GEMM_SITES census, the _BF16_EXACT list) and the
-        precision flags the policy gives it (the model's bf16 bit unless exact / excluded / below _BF16_MIN_K).
-        Every GEMM entry point the program calls goes through here, so site indices stay stable"""
+        precision flags the policy gives it (the model's bf16 bit unless exact / excluded).  Every GEMM entry point
+        the program calls goes through here, so site indices stay stable"""
         i = self._gemm_i
         self._gemm_i += 1
         if _GEMM_SITES is not None:
             f = sys._getframe(2)
             f = f.f_back if f.f_code.co_name.startswith("mm_") else f
             _GEMM_SITES.append((i, f.f_code.co_name, f.f_lineno, M, N, K, exact))
-        if self.gemm_flags and not exact and i not in _BF16_EXACT and K >= _BF16_MIN_K and not (_BF16_MIN_K and ta):
-            return self.gemm_flags
-        return 0
+        return 0 if exact or i in _BF16_EXACT else self.gemm_flags
 
     def gemm(self, *args, exact=False, ws=None):
         """vc_gemm_ex on the current lane with its scratch and split-K tile counters; args are
         vc_gemm's up to bias_grad (flags at index 21 get the model's precision bit unless `exact`);
         ws = (pointer, floats): a caller-owned slab buffer instead of the lane's scratch"""
-        fl = self.site_flags(args[0], args[2], args[3], args[4], exact)
+        fl = self.site_flags(args[2], args[3], args[4], exact)
         if fl:
             args = args[:21] + (args[21] | fl,) + args[22:]
         wp, wn = ws if ws is not None else (self.scr_p, self.scr_n)
@@ -666,7 +616,7 @@ class _Program:
         """the fp32 GEMMs issued inside (on the current lane; they must be independent of each other)
         launch as one grouped grid + one grouped split-K reduce (vc_gemm_group_begin / _add / _end over
         the lane's caller-owned group state)"""
-        if not _GROUP or self._grouping is not None:   # nested: the outer group collects
+        if self._grouping is not None:   # nested: the outer group collects
             yield
             return
         grp = self.m._gemm_group_buf(self.device, self.cur)
@@ -749,8 +699,7 @@ class _Program:
         ws = self.ws
         mean, inv = ws.f(tag + ".bm", C), ws.f(tag + ".bi", C)
         self.L.vc_bn_stats_ex(self.train, M, C, X, ldx, BN_EPS, BN_MOM, mean, inv, self.BUF[pfx + ".running_mean"],
-                              self.BUF[pfx + ".running_var"], self.scr_p, self.scr_n,
-                              self._cnt[self.cur] if _BN_TICKETS else None, N_COUNTERS, self.s)
+                              self.BUF[pfx + ".running_var"], self.scr_p, self.scr_n, None, N_COUNTERS, self.s)
         return mean, inv
 
     def layernorm(self, pfx, X, R, C, tag):
@@ -761,10 +710,9 @@ class _Program:
         return Y
 
     def conv_bn_relu3(self, pfx, X, H, Cin, Cout):
-        """ms_conv_bn_relu: BN(X) -> conv3x3 valid (+bias) -> ReLU: vc_im2col3x3 (BN affine fused) +
-        vc_gemm, or the implicit GEMM vc_conv3x3_fwd (VITCNN_IMPLICIT_CONV=1, fp32)."""
+        """ms_conv_bn_relu: BN(X) -> conv3x3 valid (+bias) -> ReLU: im2col (BN affine fused) + vc_gemm."""
         B, S = self.B, (H - 2) * (H - 2)
-        if self.train and not self.implicit_conv:
+        if self.train:
             # statistics partials + (final reduction, BN apply, im2col) in one launch: vc_bn_im2col3x3
             tag, ws = pfx + ".bn", self.ws
             col = ws.f(pfx + ".col", B * S * 9 * Cin)
@@ -776,12 +724,6 @@ class _Program:
                        bias=self.P[pfx + ".conv.bias"], relu=1)
             return out
         mean, inv = self.bn_stats(pfx + ".bn", X, Cin, B * H * H, Cin, pfx + ".bn")
-        if self.implicit_conv:
-            out = self.ws.f(pfx + ".out", B * S * Cout)
-            self.L.vc_conv3x3_fwd(B, H, H, Cin, Cout, 0, X, Cin, mean, inv, self.P[pfx + ".bn.weight"],
-                                  self.P[pfx + ".bn.bias"], self.P[pfx + ".conv.weight"], self.P[pfx + ".conv.bias"], 1,
-                                  out, Cout, self.scr_p, self.scr_n, self.s)
-            return out
         col = self.ws.f(pfx + ".col", B * S * 9 * Cin)
         self.L.vc_im2col3x3(B, H, H, Cin, X, mean, inv, self.P[pfx + ".bn.weight"], self.P[pfx + ".bn.bias"], col,
                             self.s)
@@ -797,12 +739,12 @@ class _Program:
         mean, inv = ws.f(tag + ".bm", Cout), ws.f(tag + ".bi", Cout)
         out = ws.f(seq + ".out", M * Cout)
         W, bias = self.P[seq + ".0.weight"], self.P[seq + ".0.bias"]
-        if self.train and _GEMM_BNSTATS and Cin % 4 == 0 and X % 16 == 0 and W % 16 == 0:
+        if self.train and Cin % 4 == 0 and X % 16 == 0 and W % 16 == 0:
             # the BatchNorm statistics pass folded into the GEMM's epilogue (partials per 64-row tile, shift = the
             # conv bias), then one statistics + apply + ReLU launch: 2 launches instead of 3
             P_ = -(-M // 64)
             cs = ws.get(seq + ".cs", 2 * P_ * Cout, torch.float64).data_ptr()
-            fl = self.site_flags(0, M, Cout, Cin)
+            fl = self.site_flags(M, Cout, Cin)
             self.L.vc_gemm_colstats(M, Cout, Cin, X, Cin, W, Cin, bias, pre, Cout, fl, cs, self.s)
             self.L.vc_bn_apply_partials(M, Cout, pre, Cout, P_, cs, bias, BN_EPS, BN_MOM, mean, inv,
                                         self.BUF[tag + ".running_mean"], self.BUF[tag + ".running_var"],
@@ -843,24 +785,7 @@ class _Program:
         return Z
 
     def block(self, blk, pfx, X, H):
-        B, ws, P = self.B, self.ws, self.P
-        Cin, Cout, E = blk.cin, blk.cout, blk.embed
-        D, R = E // 2, math.ceil(E / 16)
-        XW = R + 32
-        L_, Hs = H * H, H - 2
-        S, Ci, Pk = Hs * Hs, Cout // 2, (Hs // 2) * (Hs // 2)
-        rows = B * L_
-        gv, mx = pfx + ".global_view", pfx + ".global_view.layers.0"
-        order, inv = self.tab[("order", H)].data_ptr(), self.tab[("inv", H)].data_ptr()
-        M = B * S
-        if _GLOBAL_FIRST:
-            # lanes 1 / 2 fork here, but their launches are captured after lane 0's global view: the graph's
-            # executor hands the kernels to the hardware queues in capture order (section 14)
-            e0 = self.mark()
-            Fg = self.global_view(blk, pfx, X, H)
-            FM, e_fm = self.block_local_branch(blk, pfx, X, H, e0)
-            self.wait(e_fm)
-            return self.fusion(pfx + ".fusion", Fg, Cout, FM, Cout, M, Cout)
+        Cout, M = blk.cout, self.B * (H - 2) * (H - 2)
         FM, e_fm = self.block_local_branch(blk, pfx, X, H)
         Fg = self.global_view(blk, pfx, X, H)
         self.wait(e_fm)
@@ -878,10 +803,6 @@ class _Program:
         rows = B * L_
         gv, mx = pfx + ".global_view", pfx + ".global_view.layers.0"
         order, inv = self.tab[("order", H)].data_ptr(), self.tab[("inv", H)].data_ptr()
-        if self._tap_dgrad(blk):
-            # the local conv's weight, tap-major, for its data gradient in the backward (lane 0 has slack here)
-            self.L.vc_conv3x3_pack(Cout, Cin, 0, P[pfx + ".local_feature.conv.weight"],
-                                   ws.f(pfx + ".local_feature.wt", Cout * 9 * ((Cin + 3) // 4 * 4)), 0.0, self.s)
         # --- hsiMamba global view (Mutimodality_Mamba7.py:419-701, :983-1017), on lane 0
         T = ws.f(pfx + ".T", rows * E)
         XZ = ws.f(pfx + ".XZ", rows * 2 * D)
@@ -903,18 +824,10 @@ class _Program:
         Y = ws.f(pfx + ".Y", NDIR * rows * D)
         # segment checkpoints of the scan state, kept for the backward (training with grad only)
         CKP = ws.f(pfx + ".CKP", self.L.vc_mamba_scan_ckpt_floats(B, L_, D, NDIR)) if self.ws_grad else None
-        if self.scan_fused:
-            # direction conv + x_proj + scan as one launch (U and XD written for the backward)
-            self.L.vc_mamba_scan_fwd_fused(B, L_, D, R, NDIR, XZ, order, P[mx + ".conv1d.weight"],
-                                           P[mx + ".conv1d.bias"], P[mx + ".x_proj.weight"],
-                                           P[mx + ".dt_proj.weight"], P[mx + ".dt_proj.bias"], P[mx + ".A_log"],
-                                           P[mx + ".D"], U, XD, Y, CKP, self.s)
-        else:
-            self.L.vc_mamba_dirconv_fwd(B, L_, D, NDIR, order, XZ, P[mx + ".conv1d.weight"],
-                                        P[mx + ".conv1d.bias"], U, self.s)
-            self.mm_nt(NDIR * rows, XW, D, U, D, P[mx + ".x_proj.weight"], D, XD, XW)
-            self.L.vc_mamba_scan_fwd(B, L_, D, R, NDIR, U, XD, order, P[mx + ".dt_proj.weight"],
-                                     P[mx + ".dt_proj.bias"], P[mx + ".A_log"], P[mx + ".D"], Y, CKP, self.s)
+        # direction conv + x_proj + scan as one launch (U and XD written for the backward)
+        self.L.vc_mamba_scan_fwd_fused(B, L_, D, R, NDIR, XZ, order, P[mx + ".conv1d.weight"], P[mx + ".conv1d.bias"],
+                                       P[mx + ".x_proj.weight"], P[mx + ".dt_proj.weight"], P[mx + ".dt_proj.bias"],
+                                       P[mx + ".A_log"], P[mx + ".D"], U, XD, Y, CKP, self.s)
         YP, YS = ws.f(pfx + ".YP", rows * D), ws.f(pfx + ".YS", rows * D)
         T2 = ws.f(pfx + ".T2", rows * E)
         CD = ws.f(pfx + ".CD", rows * Cout)
@@ -935,15 +848,15 @@ class _Program:
         Zg = self.token_learner(pfx + ".global_feature", CD, L_, Cout, S)
         return self.layernorm(pfx + ".ln3", Zg, B * S, Cout, pfx + ".Fg")
 
-    def block_local_branch(self, blk, pfx, X, H, e0=None):
-        """local feature (lane 1) || channel feature (lane 2), then the GLfusionBlock on lane 1, forked from lane 0 at
-        e0 (now if None); returns (FM, event on lane 1 after FM)."""
+    def block_local_branch(self, blk, pfx, X, H):
+        """local feature (lane 1) || channel feature (lane 2), then the GLfusionBlock on lane 1, forked from lane 0
+        here; returns (FM, event on lane 1 after FM)."""
         B, ws, P = self.B, self.ws, self.P
         Cin, Cout = blk.cin, blk.cout
         L_, Hs = H * H, H - 2
         S, Ci, Pk = Hs * Hs, Cout // 2, (Hs // 2) * (Hs // 2)
         rows = B * L_
-        e0 = self.mark() if e0 is None else e0
+        e0 = self.mark()
         # --- local feature: BN -> conv3x3 -> ReLU
         with self.lane(1, e0):
             Fl = self.conv_bn_relu3(pfx + ".local_feature", X, H, Cin, Cout)
@@ -954,10 +867,6 @@ class _Program:
                        bias=P[pfx + ".channel_feature.bias"])
             Zc = self.token_learner(pfx + ".channel_token", CF, L_, Cout, S)
             Fc = self.layernorm(pfx + ".ln4", Zc, B * S, Cout, pfx + ".Fc")
-            if _PG_LANE2 and self.lanes_on:
-                # the NonLocal phi | g projection of Fc on this lane, beside lane 1's local conv (_PG_LANE2)
-                nl = pfx + ".FusionLayer.cross_attention"
-                self.pg_proj(pfx, B * S, Ci, Cout, Fc, ws.f(pfx + ".PG", B * S * 2 * Ci))
             e_fc = self.mark()
         with self.lane(1, e_fc):
             FM = self.glfusion(pfx, Fl, Fc, Cout, S, Ci, Pk, Hs)
@@ -982,16 +891,12 @@ class _Program:
         PG = ws.f(pfx + ".PG", M * 2 * Ci)
         with self.gemm_group():
             self.mm_nt(M, Ci, Cout, Fl, Cout, P[nl + ".theta.weight"], Cout, TH, Ci, bias=P[nl + ".theta.bias"])
-            if not (_PG_LANE2 and self.lanes_on):
-                self.pg_proj(pfx, M, Ci, Cout, Fc, PG)
+            self.pg_proj(pfx, M, Ci, Cout, Fc, PG)
         PP = ws.f(pfx + ".PP", B * Pk * 2 * Ci)
         PA = ws.get(pfx + ".PA", B * Pk * 2 * Ci, torch.uint8).data_ptr()
         ATT, O = ws.f(pfx + ".ATT", M * Pk), ws.f(pfx + ".O", M * Ci)
-        if _GLF_FUSED:   # 2x2 max pool folded into the attention forward (pooled + taps kept for the backward)
-            self.L.vc_nonlocal_attn_pool_fwd(B, S, Pk, Ci, Hs, TH, PG, 2 * Ci, PP, PA, ATT, O, self.s)
-        else:
-            self.L.vc_maxpool2_fwd(B, Hs, Hs, 2 * Ci, PG, 2 * Ci, PP, PA, self.s)
-            self.L.vc_nonlocal_attn_fwd(B, S, Pk, Ci, TH, PP, ATT, O, self.s)
+        # the 2x2 max pool of phi | g inside the attention forward (pooled map + taps kept for the backward)
+        self.L.vc_nonlocal_attn_pool_fwd(B, S, Pk, Ci, Hs, TH, PG, 2 * Ci, PP, PA, ATT, O, self.s)
         WP = ws.f(pfx + ".WP", M * Cout)
         # the W projection stays fp32 in the bf16 mode: the train-mode BatchNorm after it sees a batch
         # spread small against the mean, so bf16 operands here alone move the logits by 3.3e-2 of their
@@ -1052,17 +957,19 @@ class _Program:
     # ---------------------------------------------------------------- backward
     def bn_bwd(self, pfx, tag, dY, lddy, X, ldx, relu_out, M, C, dX, lddx, beta_dx):
         ws = self.ws
-        if relu_out and _BN_RELU_AFFINE:
+        # with dx the arrival counters select the one-launch kernels
+        cnt = self._cnt[self.cur] if dX else None
+        if relu_out:
             # the ReLU decisions recomputed from X and the affine (vc_bn_bwd_relu_ex: same bits, one read less)
             self.L.vc_bn_bwd_relu_ex(self.train, M, C, dY, lddy, X, ldx, ws.f(tag + ".bm", C), ws.f(tag + ".bi", C),
                                      self.P[pfx + ".weight"], self.P[pfx + ".bias"], dX or None, lddx, beta_dx,
                                      self.G[pfx + ".weight"], self.G[pfx + ".bias"], 0.0, self.scr_p, self.scr_n,
-                                     self._cnt[self.cur] if (dX or _BN_TICKETS) else None, N_COUNTERS, self.s)
+                                     cnt, N_COUNTERS, self.s)
             return
-        self.L.vc_bn_bwd_ex(self.train, M, C, dY, lddy, X, ldx, relu_out or None, C, ws.f(tag + ".bm", C),
+        self.L.vc_bn_bwd_ex(self.train, M, C, dY, lddy, X, ldx, None, C, ws.f(tag + ".bm", C),
                             ws.f(tag + ".bi", C), self.P[pfx + ".weight"], dX or None, lddx, beta_dx,
                             self.G[pfx + ".weight"], self.G[pfx + ".bias"], 0.0, self.scr_p, self.scr_n,
-                            self._cnt[self.cur] if (dX or _BN_TICKETS) else None, N_COUNTERS, self.s)
+                            cnt, N_COUNTERS, self.s)
 
     def ln_bwd(self, pfx, tag, dY, X, R, C, dX, beta_dx, res=0, defer=False):
         """dX = beta_dx * dX + LN grad, or res + LN grad (res: a residual gradient in another buffer).
@@ -1103,15 +1010,16 @@ class _Program:
                 self.mm_nn(M, K, N, dY, lddy, self.P[wname], K, dX, K, beta=beta_dx, relu_mask=relu_mask)
 
     def _deferring(self, defer):
-        return defer and _DEFER_WGRAD and self.lanes_on and (self.cur == 0 or (self.cur == 1 and _DEFER_WGRAD1))
+        """lane 0's weight gradients are batched and issued on the weight-gradient lane at a few flush points (one
+        fork each); without lanes (lanes_bwd=False, a captured autograd backward) every one runs in place"""
+        return defer and self.lanes_on and self.cur == 0
 
     def defer_wgrad(self, defer, M, N, K, A, lda, Bm, ldb, C, ldc, bias_grad=0):
         """C[M,N] = A^T B (a weight gradient, mm_tn), now or -- defer on lane 0 with lanes on -- at the next
         flush_wgrads().  (Round 5 also queued lane 1's split-K reductions for the weight-gradient lane: 1.74 ->
         2.0-2.1 ms, profiles/r05_ab_defer_reduce.log; removed with its ABI in round 6.)"""
         if self._deferring(defer):
-            (self.pending_wgrads if self.cur == 0 else self.pending_wgrads1).append(
-                lambda: self.mm_tn(M, N, K, A, lda, Bm, ldb, C, ldc, bias_grad=bias_grad))
+            self.pending_wgrads.append(lambda: self.mm_tn(M, N, K, A, lda, Bm, ldb, C, ldc, bias_grad=bias_grad))
             return
         self.mm_tn(M, N, K, A, lda, Bm, ldb, C, ldc, bias_grad=bias_grad)
 
@@ -1129,22 +1037,9 @@ class _Program:
             self.wgrad_tail = self.mark()
         self.pending_wgrads = []
 
-    def flush_wgrads1(self):
-        """lane 1's queued weight gradients (the GLfusion / local / channel chains' 1x1 and 3x3 convs) on
-        WGRAD1_LANE, forked from lane 1 at the end of its block chain: lane 1 keeps only the data gradients"""
-        if not self.pending_wgrads1:
-            return
-        e = self.mark()
-        with self.lane(WGRAD1_LANE, e):
-            with self.gemm_group():
-                for fn in self.pending_wgrads1:
-                    fn()
-            self.wgrad_tail1 = self.mark()
-        self.pending_wgrads1 = []
-
     def wgrad_events(self):
-        """the weight-gradient lanes' latest events, as a list (empty if nothing was deferred)"""
-        return [e for e in (self.wgrad_tail, self.wgrad_tail1) if e is not None]
+        """the weight-gradient lane's latest event, as a list (empty if nothing was deferred)"""
+        return [] if self.wgrad_tail is None else [self.wgrad_tail]
 
     def conv1x1_bn_relu_bwd(self, seq, X, M, Cin, Cout, dOut, dX, beta_dx, defer=False):
         ws = self.ws
@@ -1161,12 +1056,8 @@ class _Program:
         self.L.vc_cat2_bwd(M, C1, C2, dcat, 1 if C1 == C2 else 0, dX1 or None, C1, beta1, dX2 or None, C2, beta2,
                            self.s)
 
-    def _tap_dgrad(self, blk):
-        return _TAP_DGRAD and self.ws_grad and not self.implicit_conv and blk.cin % 4 == 0
-
-    def conv_bn_relu3_bwd(self, pfx, X, H, Cin, Cout, dOut, dX, beta_dx, tap=False, masked=False, defer=False):
-        """tap: the data gradient by vc_conv3x3_tap_dgrad over the tap-major weight block() packed;
-        masked: dOut has been through the ReLU backward already (its producer's GEMM epilogue)"""
+    def conv_bn_relu3_bwd(self, pfx, X, H, Cin, Cout, dOut, dX, beta_dx, masked=False):
+        """masked: dOut has been through the ReLU backward already (its producer's GEMM epilogue)"""
         B, ws = self.B, self.ws
         S = (H - 2) * (H - 2)
         if masked:
@@ -1176,26 +1067,10 @@ class _Program:
             dpre = ws.f(pfx + ".dpre", B * S * Cout)
             self.L.vc_relu_bwd(B * S * Cout, dOut, out, dpre, self.s)
         dxbn = ws.f(pfx + ".dxbn", B * H * H * Cin)
-        if self.implicit_conv:
-            tag = pfx + ".bn"
-            self.L.vc_conv3x3_wgrad(B, H, H, Cin, Cout, 0, X, Cin, ws.f(tag + ".bm", Cin), ws.f(tag + ".bi", Cin),
-                                    self.P[tag + ".weight"], self.P[tag + ".bias"], dpre, Cout, 0.0,
-                                    self.G[pfx + ".conv.weight"], self.G[pfx + ".conv.bias"], self.scr_p, self.scr_n,
-                                    self.s)
-            self.L.vc_conv3x3_dgrad(B, H, H, Cin, Cout, 0, dpre, Cout, self.P[pfx + ".conv.weight"], 0.0, dxbn, Cin,
-                                    self.scr_p, self.scr_n, self.s)
-        elif tap:
-            col = ws.f(pfx + ".col", B * S * 9 * Cin)
-            self.linear_bwd(pfx + ".conv.weight", pfx + ".conv.bias", dpre, B * S, Cout, 9 * Cin, col, 9 * Cin, 0, 0.0)
-            self.L.vc_conv3x3_tap_dgrad(B, H, H, Cin, Cout, 0, dpre, Cout,
-                                        ws.f(pfx + ".wt", Cout * 9 * ((Cin + 3) // 4 * 4)), 0.0, dxbn, Cin,
-                                        self.scr_p, self.scr_n, self.s)
-        else:
-            col = ws.f(pfx + ".col", B * S * 9 * Cin)
-            dcol = ws.f(pfx + ".dcol", B * S * 9 * Cin)
-            self.linear_bwd(pfx + ".conv.weight", pfx + ".conv.bias", dpre, B * S, Cout, 9 * Cin, col, 9 * Cin, dcol,
-                            0.0, defer=defer)
-            self.L.vc_col2im3x3(B, H, H, Cin, dcol, dxbn, self.s)
+        col = ws.f(pfx + ".col", B * S * 9 * Cin)
+        dcol = ws.f(pfx + ".dcol", B * S * 9 * Cin)
+        self.linear_bwd(pfx + ".conv.weight", pfx + ".conv.bias", dpre, B * S, Cout, 9 * Cin, col, 9 * Cin, dcol, 0.0)
+        self.L.vc_col2im3x3(B, H, H, Cin, dcol, dxbn, self.s)
         self.bn_bwd(pfx + ".bn", pfx + ".bn", dxbn, Cin, X, Cin, 0, B * H * H, Cin, dX, Cin, beta_dx)
 
     def token_learner_bwd(self, pfx, X, L_, C, S, dZ, dX):
@@ -1237,50 +1112,40 @@ class _Program:
         with self.lane(1, e0):
             # GLfusionBlock FusionLayer + non-local branch (lane 1) -> dFc, dFl
             CAT1, dCAT1 = f(pfx + ".CAT1", M * 2 * Cout), f(pfx + ".dCAT1", M * 2 * Cout)
-            self.conv1x1_bn_relu_bwd(pfx + ".FusionLayer.FusionLayer", CAT1, M, 2 * Cout, Cout, dFM, dCAT1, 0.0,
-                                     defer=True)
+            self.conv1x1_bn_relu_bwd(pfx + ".FusionLayer.FusionLayer", CAT1, M, 2 * Cout, Cout, dFM, dCAT1, 0.0)
             dFc, dFl = f(pfx + ".dFc", M * Cout), f(pfx + ".dFl", M * Cout)
-            if _GLF_FUSED:
-                self.L.vc_add2_2d_dup(M, Cout, dCAT1, 2 * Cout, dCAT1 + F32 * Cout, 2 * Cout, dFc, Cout, dFl, Cout,
-                                      self.s)
-            else:
-                self.L.vc_add2_2d(M, Cout, dCAT1, 2 * Cout, dCAT1 + F32 * Cout, 2 * Cout, dFc, Cout, 0.0, self.s)
-                self.L.vc_add2_2d(M, Cout, dFc, Cout, 0, 0, dFl, Cout, 0.0, self.s)
+            # the concat gradient's two halves added, the sum written to dFc and dFl: one launch
+            self.L.vc_add2_2d_dup(M, Cout, dCAT1, 2 * Cout, dCAT1 + F32 * Cout, 2 * Cout, dFc, Cout, dFl, Cout, self.s)
             # localf = BN(W o) + Fc + Fl  ->  non-local branch
             WP, dWP = f(pfx + ".WP", M * Cout), f(pfx + ".dWP", M * Cout)
             self.bn_bwd(nl + ".W.1", pfx + ".W1", dCAT1, 2 * Cout, WP, Cout, 0, M, Cout, dWP, Cout, 0.0)
             O, dO = f(pfx + ".O", M * Ci), f(pfx + ".dO", M * Ci)
-            self.linear_bwd(nl + ".W.0.weight", nl + ".W.0.bias", dWP, M, Cout, Ci, O, Ci, dO, 0.0, defer=True)
+            self.linear_bwd(nl + ".W.0.weight", nl + ".W.0.bias", dWP, M, Cout, Ci, O, Ci, dO, 0.0)
             TH, PP, ATT = f(pfx + ".TH", M * Ci), f(pfx + ".PP", B * Pk * 2 * Ci), f(pfx + ".ATT", M * Pk)
             dTH, dPP = f(pfx + ".dTH", M * Ci), f(pfx + ".dPP", B * Pk * 2 * Ci)
             dPG = f(pfx + ".dPG", M * 2 * Ci)
             PA = ws.get(pfx + ".PA", B * Pk * 2 * Ci, torch.uint8).data_ptr()
-            if _GLF_FUSED:   # attention backward with the 2x2 max-pool backward folded in (dPP: fallback only)
-                self.L.vc_nonlocal_attn_pool_bwd(B, S, Pk, Ci, Hs, TH, PP, ATT, dO, PA, dTH, dPP, dPG, self.s)
-            else:
-                self.L.vc_nonlocal_attn_bwd(B, S, Pk, Ci, TH, PP, ATT, dO, dTH, dPP, self.s)
-                self.L.vc_maxpool2_bwd(B, Hs, Hs, 2 * Ci, dPP, PA, dPG, 2 * Ci, self.s)
+            # attention backward with the 2x2 max-pool backward folded in (dPP: the kernel's fallback only)
+            self.L.vc_nonlocal_attn_pool_bwd(B, S, Pk, Ci, Hs, TH, PP, ATT, dO, PA, dTH, dPP, dPG, self.s)
             # phi | g (stacked, one weight + one data gradient; or, where the flat layout could not keep them
             # adjacent, phi then g from the two column halves of dPG) and theta: one grouped launch
             with self.gemm_group():
                 if self.m._pg_stacked[pfx]:
-                    self.linear_bwd(nl + ".phi.0.weight", nl + ".phi.0.bias", dPG, M, 2 * Ci, Cout, Fc, Cout, dFc, 1.0,
-                                    defer=True)
+                    self.linear_bwd(nl + ".phi.0.weight", nl + ".phi.0.bias", dPG, M, 2 * Ci, Cout, Fc, Cout, dFc, 1.0)
                 else:
                     self.linear_bwd(nl + ".phi.0.weight", nl + ".phi.0.bias", dPG, M, Ci, Cout, Fc, Cout, dFc, 1.0,
-                                    lddy=2 * Ci, defer=True)
+                                    lddy=2 * Ci)
                 # dFl's last contribution; its epilogue applies the local conv's ReLU backward (mask Fl)
                 self.linear_bwd(nl + ".theta.weight", nl + ".theta.bias", dTH, M, Ci, Cout, Fl, Cout, dFl, 1.0,
-                                relu_mask=Fl, defer=True)
+                                relu_mask=Fl)
             if not self.m._pg_stacked[pfx]:
                 # g's data gradient accumulates into dFc after phi's: a launch of its own, in program order
                 self.linear_bwd(nl + ".g.0.weight", nl + ".g.0.bias", dPG + F32 * Ci, M, Ci, Cout, Fc, Cout, dFc, 1.0,
-                                lddy=2 * Ci, defer=True)
+                                lddy=2 * Ci)
             side = self.lanes_on and _CH_LANE != 1
             e_pg = self.mark() if side else None
             # local feature: BN -> conv3x3 -> ReLU backward (first accumulation into dX)
-            self.conv_bn_relu3_bwd(pfx + ".local_feature", X, H, Cin, Cout, dFl, dX or 0, 1.0, tap=self._tap_dgrad(blk),
-                                   masked=True, defer=True)
+            self.conv_bn_relu3_bwd(pfx + ".local_feature", X, H, Cin, Cout, dFl, dX or 0, 1.0, masked=True)
             e_loc = self.mark() if side else None
         # channel feature: ln4 -> TokenLearner -> conv1x1, after the local chain on lane 1 (or, measurement
         # switch _CH_LANE, on a lane of its own beside it: see _CH_ORDERED)
@@ -1293,12 +1158,11 @@ class _Program:
                 self.wait(e_loc)   # the dX accumulations in program order: local, then channel
             with self.gemm_group():
                 self.linear_bwd(pfx + ".channel_feature.weight", pfx + ".channel_feature.bias", dCF, rows, Cout,
-                                Cin, X, Cin, 0, 0.0, defer=True)
+                                Cin, X, Cin, 0, 0.0)
                 if dX:
                     self.mm_nn(rows, Cin, Cout, dCF, Cout, self.P[pfx + ".channel_feature.weight"], Cin, dX, Cin,
                                beta=1.0)
             e_ch = (self.mark(), e_loc) if side else (self.mark(),)
-            self.flush_wgrads1()   # lane 1's weight gradients, beside lane 0's chain
         # global feature: ln3 -> TokenLearner -> change_dim
         Zg, dZg = f(pfx + ".global_feature.Z", M * Cout), f(pfx + ".dZg", M * Cout)
         self.ln_bwd(pfx + ".ln3", pfx + ".Fg", dFg, Zg, M, Cout, dZg, 0.0, defer=True)
@@ -1306,12 +1170,13 @@ class _Program:
         self.token_learner_bwd(pfx + ".global_feature", CD, L_, Cout, S, dZg, dCD)
         Gm, dG = f(pfx + ".G", rows * E), f(pfx + ".dG", rows * E)
         # hsiMamba: ln1 -> out_proj -> scan/combine -> x_proj/dt_proj -> conv -> in_proj -> pre_norm -> patch_embed
+        nr, nseq = NDIR * rows, NDIR * B
         T2, dT = f(pfx + ".T2", rows * E), f(pfx + ".dT", rows * E)
         YS, dYS = f(pfx + ".YS", rows * D), f(pfx + ".dYS", rows * D)
-        U, XD, XZ = f(pfx + ".U", NDIR * rows * D), f(pfx + ".XD", NDIR * rows * XW), f(pfx + ".XZ", rows * 2 * D)
-        Y, YP = f(pfx + ".Y", NDIR * rows * D), f(pfx + ".YP", rows * D)
-        dU, dDTL = f(pfx + ".dU", NDIR * rows * D), f(pfx + ".dDTL", NDIR * rows * D)
-        dXD, dXZ, dYP = f(pfx + ".dXD", NDIR * rows * XW), f(pfx + ".dXZ", rows * 2 * D), f(pfx + ".dYP", rows * D)
+        U, XD, XZ = f(pfx + ".U", nr * D), f(pfx + ".XD", nr * XW), f(pfx + ".XZ", rows * 2 * D)
+        Y, YP = f(pfx + ".Y", nr * D), f(pfx + ".YP", rows * D)
+        dU, dDTL = f(pfx + ".dU", nr * D), f(pfx + ".dDTL", nr * D)
+        dXD, dXZ, dYP = f(pfx + ".dXD", nr * XW), f(pfx + ".dXZ", rows * 2 * D), f(pfx + ".dYP", rows * D)
         if self._chain_back_bwd_ok(blk):
             # change_dim / ln1 / out_proj data gradients + the SiLU(z) gate backward in one launch; the
             # weight gradients and ln1's parameter reduction queued for the weight-gradient lane
@@ -1332,53 +1197,10 @@ class _Program:
             # SiLU(z) gate (token-wise): dyp and the z half of dxz
             self.L.vc_mamba_gate_bwd(B, L_, D, XZ, YP, dYS, dYP, dXZ, self.s)
         self.flush_wgrads()   # fusion, change_dim, out_proj: alongside the scan backward
+        # scan backward + dt_proj / x_proj data gradients + conv1d / SiLU backward in one launch; the per-sequence
+        # dA_log / D / gate and conv1d partials stay in buffers of their own
         CKPb = f(pfx + ".CKP", self.L.vc_mamba_scan_ckpt_floats(B, L_, D, NDIR))
-        if self.scan_fused:
-            self._scan_bwd_fused(pfx, gv, mx, B, L_, D, R, XW, order, inv, CKPb)
-            return self._block_bwd_tail(blk, pfx, gv, mx, B, L_, E, Cin, rows, X, dX, dT, e_ch)
-        if self._deferring(True):
-            # the per-sequence dA_log / D / gate partials stay in a buffer of their own; their
-            # reductions go with the next weight-gradient flush
-            nseq = NDIR * B
-            spn = nseq * D * 16 + nseq * D + nseq
-            sp = f(pfx + ".scanpart", spn)
-            self.L.vc_mamba_scan_bwd(B, L_, D, R, NDIR, U, XD, order, P[mx + ".dt_proj.weight"],
-                                     P[mx + ".dt_proj.bias"], P[mx + ".A_log"], P[mx + ".D"], P[gv + ".weights"], Y,
-                                     dYP, CKPb, dU, dDTL, dXD, None, None, None, sp, spn, self.s)
-            gl, ga, gd, gg = P[gv + ".weights"], G[mx + ".A_log"], G[mx + ".D"], G[gv + ".weights"]
-            self.pending_wgrads.append(
-                lambda: self.L.vc_mamba_scan_bwd_params(B, D, NDIR, gl, sp, ga, gd, gg, self.scr_p, self.scr_n,
-                                                        self.s))
-        else:
-            self.L.vc_mamba_scan_bwd(B, L_, D, R, NDIR, U, XD, order, P[mx + ".dt_proj.weight"],
-                                     P[mx + ".dt_proj.bias"], P[mx + ".A_log"], P[mx + ".D"], P[gv + ".weights"], Y,
-                                     dYP, CKPb, dU, dDTL, dXD, G[mx + ".A_log"], G[mx + ".D"], G[gv + ".weights"],
-                                     self.scr_p, self.scr_n, self.s)
-        nr = NDIR * rows
-        # dt_proj: dt_lin = xdbl[:, :R] W_dt^T + b_dt
-        # (the weight gradient reads dDTL and XD's dt-rank columns; the data gradient writes dXD's)
-        self.defer_wgrad(True, D, R, nr, dDTL, D, XD, XW, G[mx + ".dt_proj.weight"], R, G[mx + ".dt_proj.bias"])
-        self.mm_nn(nr, R, D, dDTL, D, P[mx + ".dt_proj.weight"], R, dXD, XW)
-        # x_proj: xdbl = u W_x^T
-        self.linear_bwd(mx + ".x_proj.weight", None, dXD, nr, XW, D, U, D, dU, 1.0, defer=True)
-        self.L.vc_mamba_dirconv_bwd(B, L_, D, NDIR, order, inv, XZ, P[mx + ".conv1d.weight"], P[mx + ".conv1d.bias"],
-                                    dU, dXZ, G[mx + ".conv1d.weight"], G[mx + ".conv1d.bias"], self.scr_p,
-                                    self.scr_n, self.s)
-        self._block_bwd_tail(blk, pfx, gv, mx, B, L_, E, Cin, rows, X, dX, dT, e_ch)
-
-    def _scan_bwd_fused(self, pfx, gv, mx, B, L_, D, R, XW, order, inv, CKPb):
-        """scan backward + dt_proj / x_proj data gradients + conv1d / SiLU backward in one launch
-        (vc_mamba_scan_bwd_fused), the direction gather into dxz, and the parameter gradients (dt_proj,
-        x_proj, conv1d, A_log / D / gate) queued for the weight-gradient lane"""
-        P, G, f = self.P, self.G, self.ws.f
-        rows = B * L_
-        nr, nseq = NDIR * rows, NDIR * B
-        U, XD, XZ = f(pfx + ".U", nr * D), f(pfx + ".XD", nr * XW), f(pfx + ".XZ", rows * 2 * D)
-        Y, dYP = f(pfx + ".Y", nr * D), f(pfx + ".dYP", rows * D)
-        dU, dDTL, dXD, dXZ = f(pfx + ".dU", nr * D), f(pfx + ".dDTL", nr * D), f(pfx + ".dXD", nr * XW), f(
-            pfx + ".dXZ", rows * 2 * D)
         CP = f(pfx + ".convpart", nseq * 5 * D)
-        defer = self._deferring(True)
         spn = nseq * D * 16 + nseq * D + nseq
         sp = f(pfx + ".scanpart", spn)
         gl, ga, gd, gg = P[gv + ".weights"], G[mx + ".A_log"], G[mx + ".D"], G[gv + ".weights"]
@@ -1388,26 +1210,23 @@ class _Program:
                                        dDTL, dXD, CP, None, None, None, sp, spn, self.s)
         cw, cb = G[mx + ".conv1d.weight"], G[mx + ".conv1d.bias"]
         # A_log, D, gate and conv1d parameter gradients: one reduction launch (the same order deferred or not), on the
-        # weight-gradient lane when deferring (round 6; _ONE_PARAM_REDUCE = False: the round-5 launches)
-        if _ONE_PARAM_REDUCE:
-            params = lambda: self.L.vc_mamba_bwd_params(B, D, NDIR, gl, sp, CP, ga, gd, gg, cw, cb, self.s)  # noqa: E731
-        else:
-            def params():
-                self.L.vc_mamba_scan_bwd_params(B, D, NDIR, gl, sp, ga, gd, gg, self.scr_p, self.scr_n, self.s)
-                self.L.vc_mamba_conv_params(B, D, NDIR, CP, cw, cb, self.s)
-        if defer:
+        # weight-gradient lane when deferring
+        params = lambda: self.L.vc_mamba_bwd_params(B, D, NDIR, gl, sp, CP, ga, gd, gg, cw, cb, self.s)  # noqa: E731
+        if self._deferring(True):
             self.pending_wgrads.append(params)
         else:
             params()
+        # the direction gather into dxz
         self.L.vc_mamba_dirconv_bwd_gather(B, L_, D, NDIR, inv, P[mx + ".conv1d.weight"], dU, dXZ, self.s)
-        # parameter gradients: dt_proj (dDTL, XD's dt-rank columns), x_proj (dXD, U), conv1d (partials)
+        # weight gradients: dt_proj (dDTL, XD's dt-rank columns), x_proj (dXD, U)
         self.defer_wgrad(True, D, R, nr, dDTL, D, XD, XW, G[mx + ".dt_proj.weight"], R, G[mx + ".dt_proj.bias"])
         self.defer_wgrad(True, XW, D, nr, dXD, XW, U, D, G[mx + ".x_proj.weight"], D)
+        self._block_bwd_tail(blk, pfx, gv, mx, B, L_, E, Cin, rows, X, dX, dT, e_ch)
 
     def _chain_ok(self, blk):
         """the row-chain launches apply to this block's widths (rowchain.hip limits)"""
         E = blk.embed
-        return (self.row_chain and blk.cin <= 256 and blk.cin % 4 == 0 and E <= 256 and E % 4 == 0
+        return (blk.cin <= 256 and blk.cin % 4 == 0 and E <= 256 and E % 4 == 0
                 and (E // 2) % 4 == 0 and blk.cout <= 256)
 
     def _chain_back_bwd_ok(self, blk):
@@ -1453,10 +1272,10 @@ class _Program:
                 self.mm_nn(rows, Cin, E, dTt, E, P[gv + ".patch_embed.projection.weight"], Cin, dX, Cin, beta=1.0)
         # pos_embed and patch_embed weight gradients: off the critical path
         e = self.mark()
-        with self.lane(WGRAD_LANE if _DEFER_WGRAD else 0, e):
+        with self.lane(WGRAD_LANE, e):
             self.colsum(B, L_ * E, dTt, L_ * E, G[gv + ".pos_embed"])
             self.mm_tn(E, Cin, rows, dTt, E, X, Cin, G[gv + ".patch_embed.projection.weight"], Cin)
-            if self.lanes_on and _DEFER_WGRAD:
+            if self.lanes_on:
                 self.wgrad_tail = self.mark()
 
     def bucket_ready(self, hook, name, *side_events):
@@ -1491,7 +1310,7 @@ class _Program:
                            dF2, self.G["classifier.weight"], self.G["classifier.bias"], self.s)
         dH1, dH2 = ws.f("dH1", B * S1 * C1o), ws.f("dH2", B * S2 * C2o)
         dL1, dL2 = ws.f("dL1", B * S1 * 16), ws.f("dL2", B * S2 * 32)
-        self.wgrad_tail = self.wgrad_tail1 = None
+        self.wgrad_tail = None
         self.fusion_bwd("fusion2", self.H2, C2o, self.L2, 32, B * S2, 128, dF2, dH2, 0.0, dL2, 0.0, defer=True)
         e_f2 = self.mark()
         with self.lane(3, e_f2):  # fusion1 + LiDAR branch on lane 3
