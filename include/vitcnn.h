@@ -572,6 +572,25 @@ VC_API int vc_center_accumulate(int W, int H, int P, int ncls, const int* corner
 VC_API int vc_patch_noise(int n, int C, int P, int H, float* x, const float* lab, const float* rad,
                           const float* mix, const int* off, const int* pix, int nlab, const float* cube,
                           unsigned long long seed, long long gid0, hipStream_t stream);
+/* vc_patch_gather over explicit corners whose windows may leave the scene by up to P / 2 on each side: the
+ * reference's utils.padding_image (np.pad of P // 2, utils.py:320-344) folded into the gather's addresses, so no
+ * padded copy of the cube exists.  border: 1 symmetric, 2 reflect, 3 constant zero, with np.pad's meaning -- for an
+ * axis of length L and an index i outside [0, L): symmetric reads -i - 1 / 2L - 1 - i, reflect reads -i / 2L - 2 - i,
+ * constant reads 0.0f.  corners (required) hold each window's top-left corner in scene coordinates, every component in
+ * [-(P / 2), L - P + P / 2]; the result is defined for such corners only, but for ANY corner value the mapped index
+ * is clamped into [0, L) last, so the kernel never reads outside the cube.  Output layout and xform codes are
+ * vc_patch_gather's, and where no window leaves the scene the output equals vc_patch_gather's bit for bit.
+ * Refused (status 1, before any launch): border outside 1..3 (0 = "no border" is vc_patch_gather: only its
+ * caller can promise in-scene corners), W < P or H < P, reflect on an axis shorter than 2, null corners, and
+ * vc_patch_gather's LDS bound. */
+VC_API int vc_patch_gather_border(int W, int H, int C, int P, const float* cube, const int* corners, int n,
+                                  const unsigned char* xform, int border, float* out, hipStream_t stream);
+/* labels[(x + P/2) * H + (y + P/2)] = argmax_k logits[i][k] for each window i with corner (x, y) = corners[2i..2i+1]
+ * (np.argmax of main.py:504 on the centre-pixel rows, without the probability map): the first maximum wins and a NaN
+ * counts as the maximum, as in numpy.  A centre outside the scene (even P at the far edge) is skipped; the caller
+ * supplies distinct centres.  labels: int64 [W][H]; 1 <= ncls <= 64 (the confusion matrix's bound). */
+VC_API int vc_center_argmax(int W, int H, int P, int ncls, const int* corners, int n, const float* logits,
+                            long long* labels, hipStream_t stream);
 
 /* ---------------------------------------------------------------- classification metrics
  * Confusion matrix of a prediction map (utils.py:585-663 metrics(), counting step :596-611):

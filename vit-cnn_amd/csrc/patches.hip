@@ -78,6 +78,74 @@ __global__ __launch_bounds__(256) void patch_gather(Win w, int C, const float* _
   }
 }
 
+// np.pad's index map for one axis of length n (border 1 symmetric, 2 reflect; 3 constant keeps i and reports
+// inside = false).  A window leaves the scene by at most P / 2 <= n / 2, so one reflection lands inside; the final
+// clamp makes that hold for corner values outside the contract too: whatever the corner table holds, the address
+// stays inside the cube.
+__device__ __forceinline__ int border_index(long i, int n, int border, bool& inside) {
+  inside = i >= 0 && i < n;
+  if (!inside) {
+    if (border == 1) i = i < 0 ? -i - 1 : 2L * n - 1 - i;
+    else if (border == 2) i = i < 0 ? -i : 2L * n - 2 - i;
+  }
+  return (int)min(max(i, 0L), (long)n - 1);
+}
+
+// patch_gather with the border's index map on the load side; the LDS tile and the store side are the same
+__global__ __launch_bounds__(256) void patch_gather_border(Win w, int C, const float* __restrict__ cube,
+                                                           const int* __restrict__ corners,
+                                                           const unsigned char* __restrict__ xform, int border,
+                                                           float* __restrict__ out) {
+  extern __shared__ float tile[];  // [P*P][CT+1]
+  const int P = w.P, PP = P * P;
+  const long i = blockIdx.x;
+  const long x = corners[2 * i], y = corners[2 * i + 1];
+  const int code = xform ? xform[i] : 0;
+  float* o = out + i * (long)C * PP;
+  for (int c0 = 0; c0 < C; c0 += CT) {
+    const int cn = min(CT, C - c0);
+    for (int e = threadIdx.x; e < PP * cn; e += blockDim.x) {
+      const int p = e / cn, c = e - p * cn;
+      const int ii = p / P, jj = p - ii * P;
+      bool in_x, in_y;
+      const int gx = border_index(x + ii, w.W, border, in_x);
+      const int gy = border_index(y + jj, w.H, border, in_y);
+      const float v = cube[((long)gx * w.H + gy) * C + c0 + c];
+      tile[p * (CT + 1) + c] = (border == 3 && !(in_x && in_y)) ? 0.f : v;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < cn * PP; e += blockDim.x) {
+      const int c = e / PP, q = e - c * PP;
+      const int oi = q / P, oj = q - oi * P;
+      int si, sj;
+      src_of(code, P, oi, oj, si, sj);
+      o[(long)(c0 + c) * PP + q] = tile[(si * P + sj) * (CT + 1) + c];
+    }
+    __syncthreads();
+  }
+}
+
+// one thread per window: np.argmax over its ncls logits (first maximum; the first NaN wins)
+__global__ void center_argmax(Win w, int ncls, const int* __restrict__ corners, int n,
+                              const float* __restrict__ logits, long long* __restrict__ labels) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int h = w.P / 2;
+  const long cx = (long)corners[2 * i] + h, cy = (long)corners[2 * i + 1] + h;
+  if (cx < 0 || cx >= w.W || cy < 0 || cy >= w.H) return;
+  const float* l = logits + (long)i * ncls;
+  float bv = l[0];
+  int best = 0;
+  for (int k = 1; k < ncls; ++k) {
+    const float v = l[k];
+    if (bv == bv && (v > bv || v != v)) {
+      bv = v;
+      best = k;
+    }
+  }
+  labels[cx * w.H + cy] = best;
+}
+
 __global__ void center_accumulate(Win w, int ncls, const int* __restrict__ corners, long k0, int n,
                                   const float* __restrict__ logits, double* __restrict__ probs) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -181,6 +249,32 @@ VC_EXPORT int vc_patch_gather(int W, int H, int C, int P, const float* cube, con
   const Win w = make_win(W, H, P, corners ? 1 : step);
   hipLaunchKernelGGL(patch_gather, dim3(n), dim3(256), P * P * (CT + 1) * sizeof(float), stream, w, C, cube,
                      corners, k0, xform, out);
+  VC_CHECK_LAUNCH();
+  return VC_OK;
+}
+
+VC_EXPORT int vc_patch_gather_border(int W, int H, int C, int P, const float* cube, const int* corners, int n,
+                                     const unsigned char* xform, int border, float* out, hipStream_t stream) {
+  VC_REQUIRE(border >= 1 && border <= 3);  // 0: vc_patch_gather (its caller promises in-scene corners)
+  VC_REQUIRE(P > 0 && C > 0 && W >= P && H >= P && n >= 0 && corners);
+  VC_REQUIRE(border != 2 || (W >= 2 && H >= 2));
+  VC_REQUIRE(P * P * (CT + 1) * 4 <= 64 * 1024);
+  if (n == 0) return VC_OK;
+  VC_REQUIRE(cube && out);
+  const Win w = make_win(W, H, P, 1);
+  hipLaunchKernelGGL(patch_gather_border, dim3(n), dim3(256), P * P * (CT + 1) * sizeof(float), stream, w, C, cube,
+                     corners, xform, border, out);
+  VC_CHECK_LAUNCH();
+  return VC_OK;
+}
+
+VC_EXPORT int vc_center_argmax(int W, int H, int P, int ncls, const int* corners, int n, const float* logits,
+                               long long* labels, hipStream_t stream) {
+  VC_REQUIRE(P > 0 && W >= P && H >= P && ncls >= 1 && ncls <= 64 && n >= 0);
+  if (n == 0) return VC_OK;
+  VC_REQUIRE(corners && logits && labels);
+  const Win w = make_win(W, H, P, 1);
+  hipLaunchKernelGGL(center_argmax, dim3(vc_cdiv(n, 256)), dim3(256), 0, stream, w, ncls, corners, n, logits, labels);
   VC_CHECK_LAUNCH();
   return VC_OK;
 }

@@ -15,7 +15,8 @@ from .hctnet import HCTnet  # noqa: F401
 from .s2eft import S2EFT  # noqa: F401
 from .mhst import MHST  # noqa: F401
 from .glt import GLT  # noqa: F401
+from .model_utils import evaluate, predict, test  # noqa: F401  (the end of a run: main.py:500-519)
 
 __all__ = ["Multimodality_Mamba", "CrossEntropyLoss", "Cross_fusion_CNN_Loss", "AdamW", "Adam", "MFT", "Early_fusion_CNN",
            "Middle_fusion_CNN", "Late_fusion_CNN", "Cross_fusion_CNN", "EndNet", "SpectralFormer", "HCTnet",
-           "S2EFT", "MHST", "GLT", "EndNet_Loss", "GLT_Loss", "fused_train_step"]
+           "S2EFT", "MHST", "GLT", "EndNet_Loss", "GLT_Loss", "fused_train_step", "test", "predict", "evaluate"]

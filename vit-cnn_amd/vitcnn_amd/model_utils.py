@@ -9,6 +9,9 @@ replaces, so `main.py`-style drivers switch by changing one import:
 * `save_model(savename, model, model_name, dataset_name, train_state, type, **kwargs)` — :1047-1064.
 * `test(run, net, img1, img2, hyperparams) -> probs[W, H, n_classes]` — :1067-1132.
 * `val(net, data_loader, device, supervision) -> accuracy` — :1135-1158.
+* `predict(run, net, img1, img2, hyperparams, centers=None) -> labels[W, H]` (device, int64) and
+  `evaluate(run, net, img1, img2, gt, hyperparams) -> metrics dict` — main.py:500-519 (test, argmax, metrics) on the
+  device, over the labelled pixels only; `hyperparams["border"]` mirrors the scene's edges.
 
 Registered: "Multimodality_Mamba" (the README's "ViT-CNN (ours)"), "S2EFT" (config 5, :400-423),
 "FusAtNet" (config 5, :109-118), "MFT" (:364-376) and the four MDL-RS baselines "Early_fusion_CNN",
@@ -517,7 +520,48 @@ def test(run, net, img1, img2, hyperparams):
     once; windows are gathered on the device (vc_window_gather) and the logits scattered into an
     fp64 probability map on the device (vc_center_accumulate), so the Python generator + np.copy
     per window of the reference disappears.  Returns a float64 numpy array [W, H, n_classes] like
-    the reference's `probs`."""
+    the reference's `probs`.
+
+    `hyperparams["border"]` (absent or None: as above; "symmetric", "reflect", "constant"): the run over the scene
+    padded by patch_size // 2 in that np.pad mode and cut back -- restore_from_padding(test(padding_image(img1),
+    padding_image(img2))), utils.py:320-354 -- with the padding folded into the gather's addresses, so pixels within
+    patch_size // 2 of an edge get a probability row too."""
+    return _runner(net, img1, img2, hyperparams).run(batch_size=hyperparams["batch_size"])
+
+
+def predict(run, net, img1, img2, hyperparams, centers=None):
+    """np.argmax(test(...), -1) (main.py:504) as an int64 [W, H] tensor on the device, without the probability map:
+    each window's argmax is written at its centre (vc_center_argmax), 0 where no window was evaluated.  `centers`
+    ([m, 2] integer scene pixels) evaluates only the windows centred there.  Needs test_stride 1 (ValueError)."""
+    if hyperparams.get("test_stride", 1) != 1:
+        raise ValueError(f"predict needs test_stride 1 (one window per centre), got {hyperparams['test_stride']}")
+    return _runner(net, img1, img2, hyperparams).run_labels(centers=centers, batch_size=hyperparams["batch_size"])
+
+
+def evaluate(run, net, img1, img2, gt, hyperparams):
+    """The end of a run, main.py:500-519 -- test(), np.argmax, metrics() -- evaluating only what metrics() reads: the
+    windows centred on the pixels of `gt` whose label is not in hyperparams["ignored_labels"].  The class map and the
+    confusion counts stay on the device; the result is the reference's metrics dict.  Without a border it equals
+    metrics(np.argmax(test(...), -1), gt, ignored_labels, n_classes): a labelled pixel within patch_size // 2 of an
+    edge has no window and counts as predicted 0 there too; hyperparams["border"] gives those pixels windows.
+    Needs test_stride 1 (ValueError)."""
+    from . import metrics
+    from .window import border_code
+    if hyperparams.get("test_stride", 1) != 1:
+        raise ValueError(f"evaluate needs test_stride 1 (one window per centre), got {hyperparams['test_stride']}")
+    border_code(hyperparams.get("border"))
+    gt = np.asarray(gt)
+    ignored = list(hyperparams["ignored_labels"])
+    centers = np.argwhere(~np.isin(gt, ignored))
+    pred = predict(run, net, img1, img2, hyperparams, centers=centers)
+    cm = metrics.confusion_matrix(pred, gt, ignored, hyperparams["n_classes"], device=pred.device)
+    return metrics.scores(cm.cpu().numpy())
+
+
+def _runner(net, img1, img2, hyperparams):
+    """the SlidingWindowInference of test() / predict(): PCA as model_utils.py:1076-1077, window and border options"""
+    from .window import border_code
+    border_code(hyperparams.get("border"))     # an unknown mode is refused before any work
     net.eval()
     if hyperparams.get("applyPCA", False):
         pca, k = hyperparams.get("pca"), hyperparams.get("pca_components", 3)
@@ -527,10 +571,9 @@ def test(run, net, img1, img2, hyperparams):
             from .pca import resolve
             from .window import _cube
             img1 = resolve(pca, k, _cube(img1, torch.device(hyperparams["device"])))[1]
-    runner = SlidingWindowInference(net, img1, img2, patch_size=hyperparams["patch_size"],
-                                    step=hyperparams.get("test_stride", 1), n_classes=hyperparams["n_classes"],
-                                    device=hyperparams["device"])
-    return runner.run(batch_size=hyperparams["batch_size"])
+    return SlidingWindowInference(net, img1, img2, patch_size=hyperparams["patch_size"],
+                                  step=hyperparams.get("test_stride", 1), n_classes=hyperparams["n_classes"],
+                                  device=hyperparams["device"], border=hyperparams.get("border"))
 
 
 def apply_pca(X, num_components):

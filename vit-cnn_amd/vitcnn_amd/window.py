@@ -10,6 +10,10 @@
 * `PatchBatcher` — MultiModalX (datasets.py:461-593): labelled centre pixels inside the border,
   shuffled once, batches gathered on the device with the reference's flip / rot90 augmentation
   decisions drawn on the host (datasets.py:511-526) and applied inside the gather.
+* `border=` on both -- the reference's utils.padding_image / restore_from_padding (np.pad of P // 2 around the
+  scene, utils.py:320-354) as an index map inside the gather (vc_patch_gather_border), so edge pixels are trained
+  on and classified without a padded copy of the cube; `run(centers=)` / `run_labels()` evaluate chosen pixels only
+  and write the class map on the device (vc_center_argmax).  DESIGN.md section 32.
 """
 from __future__ import annotations
 
@@ -41,8 +45,82 @@ def _cube(img, device) -> torch.Tensor:
     return t.to(device).contiguous()
 
 
+BORDER_MODES = {"symmetric": 1, "reflect": 2, "constant": 3}   # np.pad's names -> vc_patch_gather_border's codes
+
+
+def border_code(border, shape=None, patch_size=None) -> int:
+    """the gather's code of a border mode name (None: 0, no border).  An unknown name, and with the scene's `shape`
+    and `patch_size` a scene the border gather would refuse, raise ValueError here, on the host and before any launch."""
+    if border is None:
+        return 0
+    if not isinstance(border, str) or border not in BORDER_MODES:
+        raise ValueError(f"unknown border mode {border!r}: expected None or one of {sorted(BORDER_MODES)}")
+    if shape is not None:
+        W, H = int(shape[0]), int(shape[1])
+        if patch_size is not None and (W < patch_size or H < patch_size):
+            raise ValueError(f"a {W} x {H} scene is smaller than the {patch_size} x {patch_size} window")
+        if border == "reflect" and min(W, H) < 2:
+            raise ValueError(f"border='reflect' needs at least 2 pixels along each axis, the scene is {W} x {H}")
+    return BORDER_MODES[border]
+
+
+def border_index(i: int, n: int, mode: str) -> int:
+    """The pixel of an axis of length n that index i reads under np.pad's `mode` (the index map of
+    vc_patch_gather_border, restated on the host): i itself inside [0, n); outside, symmetric mirrors about the
+    edge (-i - 1, 2n - 1 - i), reflect about the edge pixel (-i, 2n - 2 - i), and constant returns -1: no pixel is
+    read, the value is 0.  Like the kernel it applies one reflection and clamps, which is exact for windows that
+    leave the scene by at most P // 2 <= n // 2."""
+    border_code(mode)
+    if 0 <= i < n:
+        return i
+    if mode == "constant":
+        return -1
+    if mode == "symmetric":
+        j = -i - 1 if i < 0 else 2 * n - 1 - i
+    else:
+        j = -i if i < 0 else 2 * n - 2 - i
+    return min(max(j, 0), n - 1)
+
+
+def _axis_corners(L: int, P: int, step: int) -> np.ndarray:
+    """sliding_window's corners along one axis (utils.py:374-397): every step-th, the last clamped to L - P"""
+    off = (L - P) % step
+    return np.minimum(np.arange(0, L - P + off + 1, step), L - P)
+
+
+def _axis_centres(L: int, P: int, step: int, bordered: bool) -> np.ndarray:
+    """the window centres along one axis in traversal order, in scene coordinates: the in-scene windows', or with a
+    border those of the axis padded by P // 2 on each side (a padded corner xp has the scene centre xp; the one
+    centre past the far edge that an even P gives is dropped)"""
+    if not bordered:
+        return _axis_corners(L, P, step) + P // 2
+    c = _axis_corners(L + 2 * (P // 2), P, step)
+    return c[c < L]
+
+
+def border_corners(W: int, H: int, P: int, step: int) -> np.ndarray:
+    """int32 [n, 2] window corners of a bordered run in scene coordinates (components from -(P // 2)): the windows of
+    the reference's sliding_window over the scene padded by P // 2 (utils.padding_image), in its order and with its
+    clamping, shifted back by P // 2, those whose centre restore_from_padding would cut away dropped."""
+    return _grid(_axis_centres(W, P, step, True), _axis_centres(H, P, step, True)) - np.int32(P // 2)
+
+
+def _grid(xs, ys) -> np.ndarray:
+    """[len(xs) * len(ys), 2] int32, x outer and y inner (sliding_window's loop order)"""
+    g = np.stack(np.meshgrid(xs, ys, indexing="ij"), axis=-1).reshape(-1, 2)
+    return np.ascontiguousarray(g, dtype=np.int32)
+
+
 class SlidingWindowInference:
-    def __init__(self, net, img1, img2, patch_size: int, step: int = 1, n_classes: int = 16, device="cuda"):
+    """`border` (None, "symmetric", "reflect" or "constant"): the run of the reference over the scene padded by
+    P // 2 with that np.pad mode and cut back afterwards -- restore_from_padding(test(padding_image(img1, [P, P],
+    mode), padding_image(img2, [P, P], mode))), utils.py:320-354 -- so that every pixel has a window; no padded
+    cube is built, the border gather mirrors the addresses."""
+
+    def __init__(self, net, img1, img2, patch_size: int, step: int = 1, n_classes: int = 16, device="cuda",
+                 border=None):
+        self.border = border_code(border, np.shape(img1) if not isinstance(img1, torch.Tensor) else img1.shape,
+                                  int(patch_size))
         self.net = net
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -54,33 +132,102 @@ class SlidingWindowInference:
             raise RuntimeError("the two modalities must cover the same image grid")
         self.P, self.step, self.ncls = int(patch_size), int(step), int(n_classes)
         self.n = window_count(self.W, self.H, self.P, self.step)
+        # with a border: the whole corner list, on the device (the sliding enumeration of vc_patch_gather knows
+        # in-scene windows only)
+        self.corners = None
+        if self.border:
+            self.corners = torch.as_tensor(border_corners(self.W, self.H, self.P, self.step)).to(self.device)
+            self.n = int(self.corners.shape[0])
 
-    @torch.no_grad()
-    def run(self, batch_size: int = 64, max_batch: int = 4096) -> np.ndarray:
-        """probs [W, H, n_classes] float64.  Windows go through the model `max(batch_size, ...)`
-        at a time (eval-mode results do not depend on the grouping)."""
+    def _corners_at(self, centers) -> torch.Tensor:
+        """int32 [m, 2] device corners of the run's windows centred at `centers` ([m, 2] scene pixels), in traversal
+        order, each once; a centre that no window of the run has (off the scene, between strides, or without a border
+        within P // 2 of an edge) is skipped"""
+        c = np.asarray(centers)
+        if c.ndim != 2 or c.shape[1] != 2 or not (c.size == 0 or np.issubdtype(c.dtype, np.integer)):
+            raise ValueError("centers must be an [m, 2] integer array of scene pixels")
+        c = c.astype(np.int64).reshape(-1, 2)
+        okx, oky = np.zeros(self.W, dtype=bool), np.zeros(self.H, dtype=bool)
+        okx[_axis_centres(self.W, self.P, self.step, bool(self.border))] = True
+        oky[_axis_centres(self.H, self.P, self.step, bool(self.border))] = True
+        c = c[(c[:, 0] >= 0) & (c[:, 0] < self.W) & (c[:, 1] >= 0) & (c[:, 1] < self.H)]
+        c = c[okx[c[:, 0]] & oky[c[:, 1]]]
+        c = np.unique(c, axis=0) if len(c) else c     # row-major, i.e. x outer and y inner: the traversal's order
+        return torch.as_tensor(np.ascontiguousarray(c - self.P // 2, dtype=np.int32)).to(self.device)
+
+    def _traverse(self, corners, batch_size, max_batch, sink):
+        """gather -> eval forward -> sink(corner pointer or None, k0, n, logits pointer, stream) per batch of windows:
+        `corners` None walks the in-scene sliding enumeration (no border), a device [n, 2] tensor those windows"""
         L = lib()
         self.net.eval()
-        bs = max(int(batch_size), min(int(max_batch), self.n))
-        probs = torch.zeros(self.W, self.H, self.ncls, dtype=torch.float64, device=self.device)
+        total = self.n if corners is None else int(corners.shape[0])
+        bs = max(int(batch_size), min(int(max_batch), total))
         C1, C2, P = int(self.c1.shape[2]), int(self.c2.shape[2]), self.P
         buf1 = torch.empty(bs, C1, P, P, device=self.device)
         buf2 = torch.empty(bs, C2, P, P, device=self.device)
         s = torch.cuda.current_stream(self.device).cuda_stream
-        for k0 in range(0, self.n, bs):
-            n = min(bs, self.n - k0)
+        for k0 in range(0, total, bs):
+            n = min(bs, total - k0)
             x1, x2 = buf1[:n], buf2[:n]
-            L.vc_patch_gather(self.W, self.H, C1, P, self.c1.data_ptr(), None, k0, self.step, n, None,
-                              x1.data_ptr(), s)
-            L.vc_patch_gather(self.W, self.H, C2, P, self.c2.data_ptr(), None, k0, self.step, n, None,
-                              x2.data_ptr(), s)
+            if corners is None:
+                cor = None
+                L.vc_patch_gather(self.W, self.H, C1, P, self.c1.data_ptr(), None, k0, self.step, n, None,
+                                  x1.data_ptr(), s)
+                L.vc_patch_gather(self.W, self.H, C2, P, self.c2.data_ptr(), None, k0, self.step, n, None,
+                                  x2.data_ptr(), s)
+            else:
+                cor = corners[k0:k0 + n].data_ptr()
+                for C, cube, x in ((C1, self.c1, x1), (C2, self.c2, x2)):
+                    if self.border:
+                        L.vc_patch_gather_border(self.W, self.H, C, P, cube.data_ptr(), cor, n, None, self.border,
+                                                 x.data_ptr(), s)
+                    else:   # the host kept in-scene windows only
+                        L.vc_patch_gather(self.W, self.H, C, P, cube.data_ptr(), cor, 0, 0, n, None, x.data_ptr(), s)
             out = self.net(x1, x2)
             if isinstance(out, tuple):
                 out = out[0]
             out = out.detach().to(torch.float32).contiguous()
-            L.vc_center_accumulate(self.W, self.H, P, self.ncls, None, k0, self.step, n, out.data_ptr(),
-                                   probs.data_ptr(), s)
+            sink(cor, k0, n, out.data_ptr(), s)
+
+    @torch.no_grad()
+    def run(self, batch_size: int = 64, max_batch: int = 4096, centers=None) -> np.ndarray:
+        """probs [W, H, n_classes] float64.  Windows go through the model `max(batch_size, ...)`
+        at a time (eval-mode results do not depend on the grouping).  `centers` ([m, 2] integer scene pixels):
+        only the run's windows centred there are evaluated, every other row stays zero."""
+        L = lib()
+        probs = torch.zeros(self.W, self.H, self.ncls, dtype=torch.float64, device=self.device)
+        corners = self.corners if centers is None else self._corners_at(centers)
+
+        def accumulate(cor, k0, n, logits, s):
+            if cor is None:
+                L.vc_center_accumulate(self.W, self.H, self.P, self.ncls, None, k0, self.step, n, logits,
+                                       probs.data_ptr(), s)
+            else:
+                L.vc_center_accumulate(self.W, self.H, self.P, self.ncls, cor, 0, 0, n, logits, probs.data_ptr(), s)
+
+        self._traverse(corners, batch_size, max_batch, accumulate)
         return probs.cpu().numpy()
+
+    @torch.no_grad()
+    def run_labels(self, centers=None, batch_size: int = 64, max_batch: int = 4096) -> torch.Tensor:
+        """The class map int64 [W, H] on the device: argmax of each window's logits written at its centre
+        (vc_center_argmax), 0 where no window was evaluated -- np.argmax(run(...), -1) without the probability map.
+        Only at stride 1, where every centre has exactly one window."""
+        if self.step != 1:
+            raise ValueError(f"run_labels needs test_stride 1 (one window per centre), got {self.step}")
+        L = lib()
+        labels = torch.zeros(self.W, self.H, dtype=torch.int64, device=self.device)
+        if centers is not None:
+            corners = self._corners_at(centers)
+        elif self.border:
+            corners = self.corners
+        else:
+            corners = torch.as_tensor(_grid(_axis_corners(self.W, self.P, 1), _axis_corners(self.H, self.P, 1))
+                                      ).to(self.device)
+        self._traverse(corners, batch_size, max_batch,
+                       lambda cor, k0, n, logits, s: L.vc_center_argmax(self.W, self.H, self.P, self.ncls, cor, n,
+                                                                        logits, labels.data_ptr(), s))
+        return labels
 
 
 class PatchBatcher:
@@ -116,12 +263,19 @@ class PatchBatcher:
     pairing the UNshuffled label list with the shuffled index list as the surrounding code does
     (:505-506, :540-543: for class v the candidates are indices[j] over the positions j with
     labels[j] == v), and is checked only against its own CPU restatement
-    (oracle/patch_noise_oracle.py)."""
+    (oracle/patch_noise_oracle.py).
+
+    `border` (None, "symmetric", "reflect" or "constant"): with a mode, `centers` are ALL pixels whose label is not
+    ignored -- the reference's edge filter `p < x < W - p` (datasets.py:498-504) is dropped -- and a window over an
+    edge reads the scene as np.pad of P // 2 in that mode would continue it (`vc_patch_gather_border`; the label
+    windows of the mixture noise too), the reference's padding_image without a padded copy.  Shuffling, sharding,
+    augmentation draws and the noise hash are the same; `border=None` is the reference's filter and the plain gather."""
 
     def __init__(self, img1, img2, gt, patch_size: int, ignored_labels=(0,), batch_size: int = 64,
                  flip_augmentation: bool = False, device="cuda", seed: int = 0, rank: int = 0, world: int = 1,
                  name: str = "synthetic", radiation_augmentation: bool = False, mixture_augmentation: bool = False,
-                 applyPCA: bool = False, pca=None, pca_components: int = 3):
+                 applyPCA: bool = False, pca=None, pca_components: int = 3, border=None):
+        self.border = border_code(border, np.shape(gt), int(patch_size))
         self.device = torch.device(device)
         self.pca = None
         if applyPCA:   # MultiModalX (datasets.py:507-508): the HSI cube reduced to its components before any patch is cut
@@ -144,6 +298,8 @@ class PatchBatcher:
         xs, ys = np.nonzero(mask)
         p = self.P // 2
         keep = (xs > p) & (xs < gt.shape[0] - p) & (ys > p) & (ys < gt.shape[1] - p)
+        if self.border:   # every labelled pixel: windows over an edge read the mirrored scene (corners may be negative)
+            keep = np.ones_like(keep)
         idx = np.stack([xs[keep], ys[keep]], axis=1)
         labels_unshuffled = gt[idx[:, 0], idx[:, 1]].astype(np.int64)
         self.rng = np.random.RandomState(seed)
@@ -225,7 +381,6 @@ class PatchBatcher:
         return codes, rad, mix
 
     def __iter__(self):
-        L = lib()
         s = torch.cuda.current_stream(self.device).cuda_stream
         C1, C2, P = int(self.c1.shape[2]), int(self.c2.shape[2]), self.P
         for b0 in range(0, len(self.centers), self.bs):
@@ -236,14 +391,23 @@ class PatchBatcher:
             codes, rad, mix = self.decisions(n)
             xf = torch.as_tensor(codes).to(self.device) if self.flip else None
             xfp = xf.data_ptr() if xf is not None else None
-            L.vc_patch_gather(self.W, self.H, C1, P, self.c1.data_ptr(), cor.data_ptr(), 0, 0, n, xfp,
-                              x1.data_ptr(), s)
-            L.vc_patch_gather(self.W, self.H, C2, P, self.c2.data_ptr(), cor.data_ptr(), 0, 0, n, xfp,
-                              x2.data_ptr(), s)
+            self._gather(C1, self.c1, cor, n, xfp, x1, s)
+            self._gather(C2, self.c2, cor, n, xfp, x2, s)
             if rad.any() or mix.any():
                 self.apply_noise(x1, cor, xfp, rad, mix, s)
             self.gid += n
             yield x1, x2, self.labels[b0:b0 + n]
+
+    def _gather(self, C, cube, cor, n, xfp, out, stream):
+        """n windows of `cube` at the device corners `cor` into out [n, C, P, P]: vc_patch_gather, or with a border
+        the gather that mirrors reads outside the scene"""
+        L = lib()
+        if self.border:
+            L.vc_patch_gather_border(self.W, self.H, C, self.P, cube.data_ptr(), cor.data_ptr(), n, xfp, self.border,
+                                     out.data_ptr(), stream)
+        else:
+            L.vc_patch_gather(self.W, self.H, C, self.P, cube.data_ptr(), cor.data_ptr(), 0, 0, n, xfp,
+                              out.data_ptr(), stream)
 
     def apply_noise(self, x1, cor, xfp, rad, mix, stream):
         L = lib()
@@ -254,8 +418,7 @@ class PatchBatcher:
         nlab = 0
         if self.mixture:
             lab = torch.empty(n, 1, P, P, device=self.device)
-            L.vc_patch_gather(self.W, self.H, 1, P, self.gt_cube.data_ptr(), cor.data_ptr(), 0, 0, n, xfp,
-                              lab.data_ptr(), stream)
+            self._gather(1, self.gt_cube, cor, n, xfp, lab, stream)
             off, pix, nlab = self.mix_off.data_ptr(), self.mix_pix.data_ptr(), self.nlab
         L.vc_patch_noise(n, C1, P, self.H, x1.data_ptr(), lab.data_ptr() if lab is not None else None,
                          rad_d.data_ptr(), mix_d.data_ptr(), off, pix, nlab, self.c1.data_ptr(), self.noise_seed, self.gid,
