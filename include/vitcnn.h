@@ -592,6 +592,46 @@ VC_API int vc_patch_gather_border(int W, int H, int C, int P, const float* cube,
 VC_API int vc_center_argmax(int W, int H, int P, int ncls, const int* corners, int n, const float* logits,
                             long long* labels, hipStream_t stream);
 
+/* ---------------------------------------------------------------- the training feed's per-epoch randomness
+ * (vitcnn_amd.window.epoch_order / device_decisions restate both entries in numpy)
+ *
+ * vc_epoch_shuffle: one epoch's sample order -- DataLoader(shuffle=True), main.py:433-440 -- and the rank's shard of
+ * it, gathered from the full centre list on the device.
+ *   base  = mix64((seed ^ VC_SHUFFLE_DOMAIN) + epoch)        wrapping 64-bit; mix64 is the splitmix64 finaliser of
+ *   key_j = mix64(base + j) >> (64 - key_bits), j in [0, N)  vc_patch_noise
+ *   perm  = the stable argsort of key: perm[r] = j for the j with exactly r pairs (key_j', j') < (key_j, j),
+ *           compared key first and index second, so equal keys keep the smaller index first
+ *   per   = ceil(N / world);  for t in [0, per):  src = perm[(rank + t * world) % N]
+ *           corners_out[t] = corners[src], labels_out[t] = labels[src], order_out[t] = src (order_out may be NULL)
+ * which is np.resize(perm, per * world)[rank::world]; world 1 is the whole permutation.  Independent uniform keys
+ * sorted give a uniform permutation; at key_bits 64 ties do not occur in practice, smaller widths exist so that the
+ * tie-break can be exercised.  corners [N][2] int32, labels [N] int64; the outputs hold per rows and nothing is
+ * written past them.  One launch; the rank of an element is counted against all N keys (O(N^2) compares over LDS
+ * tiles of recomputed keys), once per epoch.
+ * Refused (status 1, before any launch): a null corners, labels, corners_out or labels_out; N outside
+ * 1..VC_SHUFFLE_MAX; world < 1 or rank outside [0, world); key_bits outside 1..64. */
+#define VC_SHUFFLE_MAX (1 << 17)
+#define VC_SHUFFLE_DOMAIN 0xD1B54A32D192ED03ull
+VC_API int vc_epoch_shuffle(int N, unsigned long long seed, unsigned long long epoch, int rank, int world,
+                            int key_bits, const int* corners, const long long* labels, int* corners_out,
+                            long long* labels_out, int* order_out, hipStream_t stream);
+/* vc_aug_draw: the per-sample augmentation decisions of MultiModalX.__getitem__ (datasets.py:559-568, :511-535) for
+ * samples gid0 .. gid0 + n - 1, one thread each, into the arrays vc_patch_gather* (xform) and vc_patch_noise (rad,
+ * mix) read.  dkey = mix64(seed ^ mix64(gid << 2 | 3)) -- stream 3 of the noise hash, whose streams 0..2 are
+ * vc_patch_noise's fields --; u_e = (mix64(dkey + e) >> 40) * 2^-24 for e = 0..9.
+ *   VC_AUG_FLIP:      u0 > 0.5: xform = (u1 > 0.5) | (u2 > 0.5) << 1 (both clear is an outcome)
+ *                     else u3 > 0.5: xform = (1 + min(2, (int)(3.0f * u4))) << 2; else 0
+ *   VC_AUG_RADIATION: u5 < 0.1f: rad = fmaf(0.2f, u6, 0.9f); else 0
+ *   VC_AUG_MIXTURE:   u7 < 0.2f: mix = (fmaf(0.99f, u8, 0.01f), fmaf(0.99f, u9, 0.01f)); else (0, 0)
+ * An augmentation whose flag is clear writes zeros.  Each value is one fused multiply-add of float32 operands, i.e.
+ * the exact result rounded once.  xform [n] uint8, rad [n] float, mix [n][2] float, all written in full.
+ * Refused (status 1, before any launch): n < 0, flag bits outside the three, a null output with n > 0. */
+#define VC_AUG_FLIP 1
+#define VC_AUG_RADIATION 2
+#define VC_AUG_MIXTURE 4
+VC_API int vc_aug_draw(int n, int flags, unsigned long long seed, long long gid0, unsigned char* xform, float* rad,
+                       float* mix, hipStream_t stream);
+
 /* ---------------------------------------------------------------- classification metrics
  * Confusion matrix of a prediction map (utils.py:585-663 metrics(), counting step :596-611):
  * cm[t * n_classes + p] += number of pixels with target t, prediction p, both in

@@ -160,7 +160,7 @@ __global__ void center_accumulate(Win w, int ncls, const int* __restrict__ corne
 
 // Counter-based randomness of the noise augmentations: splitmix64 finaliser over
 // (seed, global sample id, stream, element).  oracle/patch_noise_oracle.py restates it.
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
+__host__ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
   z += 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -210,6 +210,79 @@ __global__ __launch_bounds__(256) void patch_noise(int total, FastDiv fCPP, Fast
     v = (a1 * v + a2 * d2) / (a1 + a2) + 0.04f * gauss(noise_key(seed, gid, 1), c * PP + p);
   }
   x[idx] = v;
+}
+
+// One epoch's order (vitcnn.h, vc_epoch_shuffle): thread i owns element i and counts the pairs (key_j, j) below its
+// own -- its place r in the stable argsort -- against all N keys, which the block recomputes SHUF_TILE at a time into
+// LDS (every lane of a wave reads the same key: a broadcast, no bank conflict; the hash is paid once per 256
+// compares).  perm[r] = i is never stored: (per - 1) * world < N, so t * world for t in [0, per) are distinct values
+// below N and the one output row that reads perm[r] is t = d / world with d = (r - rank) mod N, if world divides d.
+constexpr int SHUF_THREADS = 256;
+constexpr int SHUF_TILE = 1024;  // keys per LDS tile (8 KB)
+
+__global__ __launch_bounds__(SHUF_THREADS) void epoch_shuffle(int N, unsigned long long base, int shift, int rank,
+                                                              int world, int per, const int* __restrict__ corners,
+                                                              const long long* __restrict__ labels,
+                                                              int* __restrict__ corners_out,
+                                                              long long* __restrict__ labels_out,
+                                                              int* __restrict__ order_out) {
+  __shared__ unsigned long long keys[SHUF_TILE];
+  const int i = blockIdx.x * SHUF_THREADS + threadIdx.x;
+  const unsigned long long ki = mix64(base + (unsigned long long)i) >> shift;
+  int r = 0;
+  for (int j0 = 0; j0 < N; j0 += SHUF_TILE) {
+    const int jn = min(SHUF_TILE, N - j0);
+    for (int e = threadIdx.x; e < jn; e += SHUF_THREADS) keys[e] = mix64(base + (unsigned long long)(j0 + e)) >> shift;
+    __syncthreads();
+    // below i the tie goes to j (kj <= ki counts), from i on it does not: the tile splits at i - j0
+    const int lo = min(max(i - j0, 0), jn);
+    int c = 0;
+#pragma unroll 8
+    for (int e = 0; e < lo; ++e) c += keys[e] <= ki;
+#pragma unroll 8
+    for (int e = lo; e < jn; ++e) c += keys[e] < ki;
+    r += c;
+    __syncthreads();
+  }
+  if (i >= N) return;
+  const int d = (int)(((long)r - rank % N + N) % N);
+  const int t = d / world;
+  if (t * world != d || t >= per) return;
+  corners_out[2 * t] = corners[2 * i];
+  corners_out[2 * t + 1] = corners[2 * i + 1];
+  labels_out[t] = labels[i];
+  if (order_out) order_out[t] = i;
+}
+
+// one thread per sample (vitcnn.h, vc_aug_draw)
+__device__ __forceinline__ float draw_u(unsigned long long dkey, int e) {
+  return (float)(mix64(dkey + (unsigned long long)e) >> 40) * (1.f / 16777216.f);
+}
+
+__global__ __launch_bounds__(256) void aug_draw(int n, int flags, unsigned long long seed, long long gid0,
+                                                unsigned char* __restrict__ xform, float* __restrict__ rad,
+                                                float* __restrict__ mix) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long dkey = noise_key(seed, gid0 + i, 3);
+  int code = 0;
+  float a = 0.f, a1 = 0.f, a2 = 0.f;
+  if (flags & VC_AUG_FLIP) {
+    if (draw_u(dkey, 0) > 0.5f) {
+      code = (draw_u(dkey, 1) > 0.5f ? 1 : 0) | (draw_u(dkey, 2) > 0.5f ? 2 : 0);
+    } else if (draw_u(dkey, 3) > 0.5f) {
+      code = (1 + min(2, (int)(3.0f * draw_u(dkey, 4)))) << 2;
+    }
+  }
+  if ((flags & VC_AUG_RADIATION) && draw_u(dkey, 5) < 0.1f) a = __builtin_fmaf(0.2f, draw_u(dkey, 6), 0.9f);
+  if ((flags & VC_AUG_MIXTURE) && draw_u(dkey, 7) < 0.2f) {
+    a1 = __builtin_fmaf(0.99f, draw_u(dkey, 8), 0.01f);
+    a2 = __builtin_fmaf(0.99f, draw_u(dkey, 9), 0.01f);
+  }
+  xform[i] = (unsigned char)code;
+  rad[i] = a;
+  mix[2 * i] = a1;
+  mix[2 * i + 1] = a2;
 }
 
 // number of sliding-window positions along one axis (utils.py:389-399)
@@ -290,6 +363,31 @@ VC_EXPORT int vc_patch_noise(int n, int C, int P, int H, float* x, const float* 
   hipLaunchKernelGGL(patch_noise, dim3(vc_cdiv(total, 256)), dim3(256), 0, stream, (int)total,
                      make_fastdiv(C * P * P), make_fastdiv(P * P), C, H, x, lab, rad, mix, off, pix, nlab, cube, seed,
                      gid0);
+  VC_CHECK_LAUNCH();
+  return VC_OK;
+}
+
+VC_EXPORT int vc_epoch_shuffle(int N, unsigned long long seed, unsigned long long epoch, int rank, int world,
+                               int key_bits, const int* corners, const long long* labels, int* corners_out,
+                               long long* labels_out, int* order_out, hipStream_t stream) {
+  VC_REQUIRE(N >= 1 && N <= VC_SHUFFLE_MAX);
+  VC_REQUIRE(world >= 1 && rank >= 0 && rank < world);
+  VC_REQUIRE(key_bits >= 1 && key_bits <= 64);
+  VC_REQUIRE(corners && labels && corners_out && labels_out);
+  const unsigned long long base = mix64((seed ^ VC_SHUFFLE_DOMAIN) + epoch);
+  const int per = (int)(((long)N + world - 1) / world);
+  hipLaunchKernelGGL(epoch_shuffle, dim3(vc_cdiv(N, SHUF_THREADS)), dim3(SHUF_THREADS), 0, stream, N, base,
+                     64 - key_bits, rank, world, per, corners, labels, corners_out, labels_out, order_out);
+  VC_CHECK_LAUNCH();
+  return VC_OK;
+}
+
+VC_EXPORT int vc_aug_draw(int n, int flags, unsigned long long seed, long long gid0, unsigned char* xform, float* rad,
+                          float* mix, hipStream_t stream) {
+  VC_REQUIRE(n >= 0 && (flags & ~(VC_AUG_FLIP | VC_AUG_RADIATION | VC_AUG_MIXTURE)) == 0);
+  if (n == 0) return VC_OK;
+  VC_REQUIRE(xform && rad && mix);
+  hipLaunchKernelGGL(aug_draw, dim3(vc_cdiv(n, 256)), dim3(256), 0, stream, n, flags, seed, gid0, xform, rad, mix);
   VC_CHECK_LAUNCH();
   return VC_OK;
 }

@@ -14,6 +14,9 @@
   scene, utils.py:320-354) as an index map inside the gather (vc_patch_gather_border), so edge pixels are trained
   on and classified without a padded copy of the cube; `run(centers=)` / `run_labels()` evaluate chosen pixels only
   and write the class map on the device (vc_center_argmax).  DESIGN.md section 32.
+* `epoch_order` / `device_decisions` -- numpy restatements of vc_epoch_shuffle and vc_aug_draw, the per-epoch
+  reshuffle and the per-sample augmentation draws that `PatchBatcher(shuffle="epoch", draws="device")` runs on the
+  device.  DESIGN.md section 33.
 """
 from __future__ import annotations
 
@@ -230,12 +233,85 @@ class SlidingWindowInference:
         return labels
 
 
+SHUFFLE_MAX = 1 << 17                   # VC_SHUFFLE_MAX: the longest list vc_epoch_shuffle orders
+SHUFFLE_DOMAIN = 0xD1B54A32D192ED03     # VC_SHUFFLE_DOMAIN: keeps the order's keys apart from the noise hash's
+AUG_FLIP, AUG_RADIATION, AUG_MIXTURE = 1, 2, 4   # VC_AUG_*: vc_aug_draw's flag bits
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z: np.ndarray) -> np.ndarray:
+    """the splitmix64 finaliser of patches.hip over a uint64 array (array arithmetic wraps modulo 2^64)"""
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _u64(v: int) -> np.ndarray:
+    return np.array([int(v) & _M64], dtype=np.uint64)
+
+
+def epoch_keys(N: int, seed: int, epoch: int, key_bits: int = 64) -> np.ndarray:
+    """uint64 [N]: key_j = mix64(base + j) >> (64 - key_bits) with base = mix64((seed ^ SHUFFLE_DOMAIN) + epoch),
+    the sort keys of vc_epoch_shuffle"""
+    if not 1 <= int(key_bits) <= 64:
+        raise ValueError(f"key_bits must be in 1..64, got {key_bits}")
+    base = _mix64(_u64((int(seed) & _M64) ^ SHUFFLE_DOMAIN) + _u64(epoch))
+    return _mix64(base + np.arange(int(N), dtype=np.uint64)) >> np.uint64(64 - int(key_bits))
+
+
+def epoch_order(N: int, seed: int, epoch: int, rank: int = 0, world: int = 1, key_bits: int = 64) -> np.ndarray:
+    """int32 [ceil(N / world)]: the source indices vc_epoch_shuffle writes as order_out -- the stable argsort of
+    `epoch_keys` (equal keys keep the smaller index first), wrapped to a multiple of `world` and cut every world-th
+    from `rank`, np.resize(perm, per * world)[rank::world].  world 1 is the whole permutation of range(N).  Numpy only:
+    an epoch's order can be reproduced without the device."""
+    N, rank, world = int(N), int(rank), int(world)
+    if not 1 <= N <= SHUFFLE_MAX:
+        raise ValueError(f"N must be in 1..{SHUFFLE_MAX}, got {N}")
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"rank {rank} is outside [0, world = {world})")
+    perm = np.argsort(epoch_keys(N, seed, epoch, key_bits), kind="stable")
+    per = -(-N // world)
+    return np.ascontiguousarray(np.resize(perm, per * world)[rank::world], dtype=np.int32)
+
+
+def device_decisions(seed: int, gid0: int, n: int, flip: bool, radiation: bool, mixture: bool):
+    """(xform codes [n] u8, radiation alpha [n] f32, mixture (a1, a2) [n, 2] f32), bit for bit what vc_aug_draw writes
+    for the samples gid0 .. gid0 + n - 1: the decision tree of MultiModalX.__getitem__ (datasets.py:559-568, :511-535)
+    over ten 24-bit uniforms u_e = (mix64(dkey + e) >> 40) * 2^-24 of the sample's key dkey = mix64(seed ^
+    mix64(gid << 2 | 3)), stream 3 of the noise hash.  Each value is one fused multiply-add of float32 operands on
+    the device; here the product and the sum are exact in float64 and rounded to float32 once, which is the same."""
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"n must not be negative, got {n}")
+    f32, f64 = np.float32, np.float64
+    gid = _u64(gid0) + np.arange(n, dtype=np.uint64)
+    dkey = _mix64(_u64(seed) ^ _mix64((gid << np.uint64(2)) | np.uint64(3)))
+    u = [(_mix64(dkey + np.uint64(e)) >> np.uint64(40)).astype(f32) * f32(2.0 ** -24) for e in range(10)]
+
+    def fma(a, x, b):
+        return (f64(f32(a)) * x.astype(f64) + f64(f32(b))).astype(f32)
+
+    codes, rad, mix = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=f32), np.zeros((n, 2), dtype=f32)
+    if flip:
+        flips = (u[1] > f32(0.5)).astype(np.uint8) | ((u[2] > f32(0.5)).astype(np.uint8) << 1)
+        rot = (1 + np.minimum(2, (f32(3.0) * u[4]).astype(np.int32))).astype(np.uint8) << 2
+        codes = np.where(u[0] > f32(0.5), flips, np.where(u[3] > f32(0.5), rot, 0)).astype(np.uint8)
+    if radiation:
+        rad = np.where(u[5] < f32(0.1), fma(0.2, u[6], 0.9), f32(0)).astype(f32)
+    if mixture:
+        on = (u[7] < f32(0.2))[:, None]
+        mix = np.where(on, np.stack([fma(0.99, u[8], 0.01), fma(0.99, u[9], 0.01)], axis=1), f32(0)).astype(f32)
+    return codes, rad, np.ascontiguousarray(mix)
+
+
 class PatchBatcher:
     """Training batches of MultiModalX patches assembled on the device.
 
     Iterating yields (hsi [B,C1,P,P], lidar [B,C2,P,P], target [B] int64) on `device`, in the
     order of the shuffled `indices` (DataLoader(shuffle=False) over the dataset; the reference's train
-    loader reshuffles every epoch, main.py:434-440, this one keeps its construction-time order).
+    loader reshuffles every epoch, main.py:434-440; this one keeps its construction-time order unless
+    `shuffle="epoch"`, below).
     `rank`/`world` select a disjoint shard for data parallelism: every rank builds the batcher with the
     same `seed` and takes every world-th centre of the padded shuffled list (equal batch counts on every
     rank; `parallel.is_sharded` sees the attributes, so train() does not shard it again).
@@ -248,8 +324,9 @@ class PatchBatcher:
 
     Augmentations of MultiModalX.__getitem__ (datasets.py:559-568), per sample in the reference's
     order and with its probabilities, the decisions drawn from one host RandomState in the reference's
-    call order: flip / rot90 (flip_augmentation, :511-526) folded into the gather; radiation noise
-    (p 0.1: alpha ~ U(0.9, 1.1), x = alpha x + N/25, :529-532) and mixture noise (p 0.2: a1, a2 ~
+    call order (or on the device, `draws="device"` below): flip / rot90 (flip_augmentation, :511-526)
+    folded into the gather; radiation noise (p 0.1: alpha ~ U(0.9, 1.1), x = alpha x + N/25, :529-532)
+    and mixture noise (p 0.2: a1, a2 ~
     U(0.01, 1), x = (a1 x + a2 d2) / (a1 + a2) + N/25 with d2 the spectra of random same-class training
     pixels, :534-545) on the HSI patch by `vc_patch_noise`.  The per-element normal fields and the
     per-pixel same-class choices (the reference's np.random.normal(size=patch) / np.random.choice) are
@@ -269,12 +346,36 @@ class PatchBatcher:
     ignored -- the reference's edge filter `p < x < W - p` (datasets.py:498-504) is dropped -- and a window over an
     edge reads the scene as np.pad of P // 2 in that mode would continue it (`vc_patch_gather_border`; the label
     windows of the mixture noise too), the reference's padding_image without a padded copy.  Shuffling, sharding,
-    augmentation draws and the noise hash are the same; `border=None` is the reference's filter and the plain gather."""
+    augmentation draws and the noise hash are the same; `border=None` is the reference's filter and the plain gather.
+
+    `shuffle="epoch"` (default None: the construction-time order, every pass): the reference's per-epoch reshuffle.
+    The whole construction-time centre list -- corners and labels, before sharding -- stays on the device, and every
+    pass starts with one `vc_epoch_shuffle` launch on the current stream that orders it for epoch `e` and gathers this
+    rank's shard into `corners` / `labels`; batch slicing is unchanged.  `e` counts the passes from 0, `set_epoch(e)`
+    sets the next pass's (DistributedSampler's convention).  With `world > 1` the shard is cut from each epoch's
+    permutation of the whole list, so samples move between ranks; every rank counts epochs alike, so the seed check of
+    `parallel.check_loader_shard` still suffices.  The order is a uniform permutation (independent 64-bit hash keys,
+    sorted), as np.random.shuffle's is, but not numpy's stream; `epoch_order` gives it on the host, and `centers` is
+    then the centre list of the current epoch's shard.  The mixture tables keep the construction-time list.  At most
+    SHUFFLE_MAX centres.
+
+    `draws="device"` (default "host": `decisions()`, one RandomState loop per batch and three uploads): the per-sample
+    flip / rot90 code, radiation alpha and mixture weights are drawn by `vc_aug_draw` from stream 3 of the noise hash
+    into device arrays that the gather and `vc_patch_noise` read -- the reference's tree and probabilities, not
+    numpy's stream (`device_decisions` restates it); no RandomState call, no upload, and with radiation or mixture
+    enabled `vc_patch_noise` is always launched (it returns early per sample on zero decisions).  DESIGN.md
+    section 33."""
 
     def __init__(self, img1, img2, gt, patch_size: int, ignored_labels=(0,), batch_size: int = 64,
                  flip_augmentation: bool = False, device="cuda", seed: int = 0, rank: int = 0, world: int = 1,
                  name: str = "synthetic", radiation_augmentation: bool = False, mixture_augmentation: bool = False,
-                 applyPCA: bool = False, pca=None, pca_components: int = 3, border=None):
+                 applyPCA: bool = False, pca=None, pca_components: int = 3, border=None, shuffle=None,
+                 draws: str = "host"):
+        if shuffle is not None and shuffle != "epoch":
+            raise ValueError(f"unknown shuffle {shuffle!r}: expected None or 'epoch'")
+        if draws not in ("host", "device"):
+            raise ValueError(f"unknown draws {draws!r}: expected 'host' or 'device'")
+        self.shuffle, self.draws = shuffle, draws
         self.border = border_code(border, np.shape(gt), int(patch_size))
         self.device = torch.device(device)
         self.pca = None
@@ -301,6 +402,8 @@ class PatchBatcher:
         if self.border:   # every labelled pixel: windows over an edge read the mirrored scene (corners may be negative)
             keep = np.ones_like(keep)
         idx = np.stack([xs[keep], ys[keep]], axis=1)
+        if self.shuffle == "epoch" and not 1 <= len(idx) <= SHUFFLE_MAX:
+            raise ValueError(f"shuffle='epoch' orders 1..{SHUFFLE_MAX} centres on the device, the scene has {len(idx)}")
         labels_unshuffled = gt[idx[:, 0], idx[:, 1]].astype(np.int64)
         self.rng = np.random.RandomState(seed)
         self.rng.shuffle(idx)
@@ -308,18 +411,29 @@ class PatchBatcher:
         if self.mixture:
             self._mixture_tables(gt, idx, labels_unshuffled)
         self.rank, self.world = int(rank), int(world)
-        if self.world > 1:
+        self.epoch = self._next_epoch = 0    # the pass `corners` / `labels` hold, and the next one (shuffle="epoch")
+        self._all_centers = None
+        if self.shuffle == "epoch":
+            # the whole list stays on the device; the shard is cut from each epoch's order of it (epoch 0's here, on
+            # the host, so that `corners` / `labels` exist before the first pass; every pass launches vc_epoch_shuffle)
+            if self.world < 1 or not 0 <= self.rank < self.world:
+                raise ValueError(f"rank {self.rank} is outside [0, world = {self.world})")
+            self._all_centers = idx
+            self._all_corners = torch.as_tensor(np.ascontiguousarray((idx - p).astype(np.int32))).to(self.device)
+            self._all_labels = torch.as_tensor(gt[idx[:, 0], idx[:, 1]].astype(np.int64)).to(self.device)
+            idx = idx[epoch_order(len(idx), self.seed, 0, self.rank, self.world)]
+        elif self.world > 1:
             # data-parallel shard: the shuffled list padded by wrapping to ceil(N / world) * world, then every
             # world-th centre from `rank` -- disjoint shards of equal length (equal batch counts: train()
             # exchanges one gradient per batch on every rank); parallel.check_loader_shard verifies that
             # every rank built its batcher from the same seed, i.e. cut its shard from the same permutation
             per = -(-len(idx) // self.world)
             idx = np.resize(idx, (per * self.world, 2))[self.rank::self.world] if len(idx) else idx
-            if self.rank > 0:
-                # augmentation draws of their own on every rank (rank 0 keeps the single-process stream)
-                self.rng = np.random.RandomState((int(seed) + 7919 * self.rank) % (1 << 32))
+        if self.world > 1 and self.rank > 0:
+            # host augmentation draws of their own on every rank (rank 0 keeps the single-process stream)
+            self.rng = np.random.RandomState((int(seed) + 7919 * self.rank) % (1 << 32))
         self.noise_seed = (self.seed ^ (0x9E3779B97F4A7C15 * self.rank)) & ((1 << 63) - 1)
-        self.centers = idx
+        self._centers = idx
         self.labels = torch.as_tensor(gt[idx[:, 0], idx[:, 1]].astype(np.int64)).to(self.device)
         corners = (idx - p).astype(np.int32)
         self.corners = torch.as_tensor(np.ascontiguousarray(corners)).to(self.device)
@@ -345,7 +459,34 @@ class PatchBatcher:
         self.gt_cube = torch.as_tensor(np.ascontiguousarray(gt, dtype=np.float32)[:, :, None]).to(self.device)
 
     def __len__(self):
-        return -(-len(self.centers) // self.bs)
+        return -(-len(self._centers) // self.bs)
+
+    @property
+    def centers(self) -> np.ndarray:
+        """[n, 2] centre pixels in the order the batches take them: the construction-time list, or with
+        shuffle="epoch" the shard of epoch `self.epoch` (the pass last started), from `epoch_order`"""
+        if self._all_centers is None:
+            return self._centers
+        return self._all_centers[epoch_order(len(self._all_centers), self.seed, self.epoch, self.rank, self.world)]
+
+    def set_epoch(self, epoch: int):
+        """the epoch whose order the next pass takes (shuffle="epoch"; later passes count on from it).  Without
+        shuffle="epoch" the order does not depend on the epoch and the call changes nothing, so a loop that calls it on
+        every loader, as for a DistributedSampler, needs no special case."""
+        self._next_epoch = int(epoch)
+
+    def _start_pass(self, stream):
+        """shuffle="epoch": order the whole list for the next epoch and gather this rank's shard, on the device.  The
+        shard goes into new tensors, so label slices handed out by an earlier pass keep their values.  The batcher
+        is iterated on ONE stream: the replaced tensors return to the caching allocator, which may hand their memory
+        out again on that stream only because everything that read them was enqueued there before."""
+        e = self._next_epoch
+        corners, labels = torch.empty_like(self.corners), torch.empty_like(self.labels)
+        lib().vc_epoch_shuffle(len(self._all_centers), self.seed, e & _M64, self.rank, self.world, 64,
+                               self._all_corners.data_ptr(), self._all_labels.data_ptr(), corners.data_ptr(),
+                               labels.data_ptr(), None, stream)
+        self.corners, self.labels = corners, labels
+        self.epoch, self._next_epoch = e, e + 1
 
     @property
     def dataset(self):
@@ -383,20 +524,39 @@ class PatchBatcher:
     def __iter__(self):
         s = torch.cuda.current_stream(self.device).cuda_stream
         C1, C2, P = int(self.c1.shape[2]), int(self.c2.shape[2]), self.P
-        for b0 in range(0, len(self.centers), self.bs):
-            n = min(self.bs, len(self.centers) - b0)
+        if self.shuffle == "epoch":
+            self._start_pass(s)
+        corners, labels = self.corners, self.labels     # this pass's: a later pass replaces them
+        total = len(self._centers)
+        flags = ((AUG_FLIP if self.flip and P > 1 else 0) | (AUG_RADIATION if self.radiation else 0)
+                 | (AUG_MIXTURE if self.mixture else 0)) if self.draws == "device" else 0
+        for b0 in range(0, total, self.bs):
+            n = min(self.bs, total - b0)
             x1 = torch.empty(n, C1, P, P, device=self.device)
             x2 = torch.empty(n, C2, P, P, device=self.device)
-            cor = self.corners[b0:b0 + n]
-            codes, rad, mix = self.decisions(n)
-            xf = torch.as_tensor(codes).to(self.device) if self.flip else None
-            xfp = xf.data_ptr() if xf is not None else None
-            self._gather(C1, self.c1, cor, n, xfp, x1, s)
-            self._gather(C2, self.c2, cor, n, xfp, x2, s)
-            if rad.any() or mix.any():
-                self.apply_noise(x1, cor, xfp, rad, mix, s)
+            cor = corners[b0:b0 + n]
+            if self.draws == "device":
+                xfp = None
+                if flags:   # all three arrays on the device, drawn there: nothing is uploaded
+                    xf = torch.empty(n, dtype=torch.uint8, device=self.device)
+                    rad_d, mix_d = torch.empty(n, device=self.device), torch.empty(n, 2, device=self.device)
+                    lib().vc_aug_draw(n, flags, self.noise_seed, self.gid, xf.data_ptr(), rad_d.data_ptr(),
+                                      mix_d.data_ptr(), s)
+                    xfp = xf.data_ptr() if flags & AUG_FLIP else None
+                self._gather(C1, self.c1, cor, n, xfp, x1, s)
+                self._gather(C2, self.c2, cor, n, xfp, x2, s)
+                if flags & (AUG_RADIATION | AUG_MIXTURE):
+                    self._noise(x1, cor, xfp, rad_d, mix_d, s)
+            else:
+                codes, rad, mix = self.decisions(n)
+                xf = torch.as_tensor(codes).to(self.device) if self.flip else None
+                xfp = xf.data_ptr() if xf is not None else None
+                self._gather(C1, self.c1, cor, n, xfp, x1, s)
+                self._gather(C2, self.c2, cor, n, xfp, x2, s)
+                if rad.any() or mix.any():
+                    self.apply_noise(x1, cor, xfp, rad, mix, s)
             self.gid += n
-            yield x1, x2, self.labels[b0:b0 + n]
+            yield x1, x2, labels[b0:b0 + n]
 
     def _gather(self, C, cube, cor, n, xfp, out, stream):
         """n windows of `cube` at the device corners `cor` into out [n, C, P, P]: vc_patch_gather, or with a border
@@ -410,10 +570,14 @@ class PatchBatcher:
                               out.data_ptr(), stream)
 
     def apply_noise(self, x1, cor, xfp, rad, mix, stream):
-        L = lib()
-        n, C1, P = x1.shape[0], x1.shape[1], self.P
+        """vc_patch_noise on x1 with the host decisions `rad` [n] / `mix` [n, 2] (numpy), uploaded here"""
         rad_d = torch.as_tensor(rad).to(self.device)
         mix_d = torch.as_tensor(np.ascontiguousarray(mix)).to(self.device)
+        self._noise(x1, cor, xfp, rad_d, mix_d, stream)
+
+    def _noise(self, x1, cor, xfp, rad_d, mix_d, stream):
+        L = lib()
+        n, C1, P = x1.shape[0], x1.shape[1], self.P
         lab = off = pix = None
         nlab = 0
         if self.mixture:
